@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: FoV-steps/sec of the flood-filling inference loop.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one full FoV step of the hot path on a device-resident canvas:
 gather -> conv0_a -> 23 x (3x3x3, 32->32) convs on the matrix pipe -> logit head ->
@@ -23,11 +23,30 @@ Rank 0 prints ONE JSON line:
   roofline      the resident conv stack (conv32ps): algorithmic flops / HIP-event
                 time of every timed step's launch against the fp16 MFMA peak / 3;
                 HBM traffic and matrix-pipe occupancy from the committed PMC
-                capture; the shader clock the box held
+                capture; (--full) the shader clock the box held
+With --full, also:
+  full_volume   the complete pass against the reference-minted runs of the same
+                volume, and the other 250^3 volume that has one (second_volume)
+  segmentation_merge, shader clock and board samples
   cpu_baseline  (N == 1) the oracle port on this host's usable cores, a bounded
                 sample of the same workload; its first steps replayed on the GPU
                 (parity_*)
   batched       (N == 1) configs[2]: --mode sharded on a 512^3 volume, 32 canvases
+  c5            (N == 1) configs[4]'s model: --mode sharded --config c5
+A plain run does only what `value` and the timed steps need: set-up, prewarm and
+warm-up, the K timed steps, the complete pass, the line.
+
+--dump-outputs DIR (stream mode) writes, after the run, what the timed path
+computed, as DIR/<name>.npy in f32 / f64 (~32 MB at most; the inputs are the same
+on every run of the same arguments):
+  steps_seed_logits, steps_seed_known    the seed logits of the segment grown at
+                the last timed step (the box its FoVs span; known = 1 where a FoV
+                was pasted, else the logit is NaN on the canvas and 0 here)
+  steps_segmentation_sample              the labels committed by then (sample)
+  steps_box_and_counts                   that box (lo zyx, hi zyx), the prewarm
+                steps and the steps counted after them (W + K)
+  full_volume_segmentation_sample        the labels of the complete pass (sample)
+Samples: the same seeded 2^21 voxels of the 250^3 volume on every run.
 """
 
 import argparse
@@ -516,6 +535,50 @@ def recorded_pass(make, policy):
   return seen, again
 
 
+DUMP_SAMPLE_VOXELS = 1 << 21  # a seeded sample of a larger volume: 8 MB as f32
+DUMP_BOX_VOXELS = 1 << 22  # the seed logits box up to 16 MB as f32, else sampled
+
+
+def volume_sample(vol, k=DUMP_SAMPLE_VOXELS, seed=0):
+  """-> f32 of a fixed, seeded sample of `vol` (the same voxels for the same shape:
+  runs of two builds compare value for value); a small volume whole."""
+  flat = np.asarray(vol).reshape(-1)
+  if flat.size > k:
+    flat = flat[np.sort(np.random.RandomState(seed).randint(0, flat.size, k))]
+  return flat.astype(np.float32)
+
+
+def step_outputs(canvas, state):
+  """What a caller of the timed path holds after its last step: the seed logits of
+  the segment being grown (the box its FoV positions span, FoV included -- the box
+  a commit would take; never predicted = NaN there, written as 0 with a 0/1 mask
+  beside it), the labels committed so far (a seeded sample) and where the box lies
+  and after how many steps (prewarm, warmup, timed)."""
+  shape = np.array(canvas.shape)
+  half = np.array(canvas._pred_size) // 2
+  lo = np.maximum(np.asarray(canvas._min_pos) - half, 0)
+  hi = np.minimum(np.asarray(canvas._max_pos) + half + 1, shape)
+  logits = np.asarray(canvas.seed[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]], np.float32)
+  if logits.size > DUMP_BOX_VOXELS:
+    logits = volume_sample(logits, DUMP_BOX_VOXELS, seed=1)
+  known = ~np.isnan(logits)
+  return {
+      'steps_seed_logits': np.where(known, logits, np.float32(0)),
+      'steps_seed_known': known.astype(np.float32),
+      'steps_segmentation_sample': volume_sample(np.asarray(canvas.segmentation)),
+      'steps_box_and_counts': np.array(
+          list(lo) + list(hi) + [state.get('prewarm_steps', 0), state['n']], np.float64),
+  }
+
+
+def write_outputs(out_dir, outputs):
+  """--dump-outputs: one DIR/<name>.npy per array."""
+  os.makedirs(out_dir, exist_ok=True)
+  for name, arr in sorted(outputs.items()):
+    assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+    np.save(os.path.join(out_dir, name + '.npy'), arr)
+
+
 def full_volume_pass(args, comm, model, exe, request, image, barrier):
   """BASELINE.json's metric on a COMPLETE pass: `Canvas.segment_all` over every
   grid seed of this rank's volume (reference inference.py:538-683; 24 k FoV
@@ -566,7 +629,8 @@ def full_volume_pass(args, comm, model, exe, request, image, barrier):
   out['seeds_tried'] = int(len(fixture['seeds'])) if fixture is not None else None
   seg = np.array(np.asarray(canvas.segmentation))
   canvas.close()
-  if fixture is not None and comm.rank == 0:
+  out['_segmentation'] = seg  # (popped by run_gpu: --dump-outputs)
+  if fixture is not None and comm.rank == 0 and args.full:
     seen, again = recorded_pass(make, policy)
     out['vs_reference_run'] = run_agreement(seg, seen, fixture_path,
                                             'the torch-CPU / oneDNN f32 forward')
@@ -577,7 +641,7 @@ def full_volume_pass(args, comm, model, exe, request, image, barrier):
   # the OTHER whole volume the suite holds a reference-minted run of (one more build of
   # a 250^3 phantom and two passes, ~15 s): rank 0, N = 1, untimed for `value`
   other = 4321 if args.workload_seed == 1234 else 1234
-  if (fixture is not None and comm.rank == 0 and comm.world == 1 and
+  if (fixture is not None and comm.rank == 0 and comm.world == 1 and args.full and
       not args.no_second_volume and os.path.exists(full_fixture(other))):
     from ffn_amd import synthetic
     image2 = synthetic.normalize(bench_volume(tuple(VOLUME_ZYX), other))
@@ -779,29 +843,31 @@ def run_gpu(args, rank, local_rank, world):
   # Final segmentation merge (the ONLY collective of the path): the N per-rank
   # volumes are treated as N sub-boxes stacked along z of one virtual volume;
   # id offsets by all_gather, union by all_reduce(MAX) over RCCL.  Untimed
-  # extra, outside the FoV-step region; reported as merge_ms.
+  # extra, outside the FoV-step region; reported as merge_ms (--full).
   merge_ms = None
   merged_ids = None
-  try:
-    from ffn_amd import distributed as ffn_dist
-    seg = np.array(canvas._handle.read_segmentation())
-    seg[seg < 0] = 0
-    full = (world * shape[0], shape[1], shape[2])
-    boxes = ffn_dist.tile_volume(full, shape, (0, 0, 0))
-    barrier()
-    tm = time.perf_counter()
-    merged, _ = ffn_dist.merge_segmentations(
-        [(boxes[rank], seg)], full, rank, world,
-        device=coll_device)
-    barrier()
-    merge_ms = (time.perf_counter() - tm) * 1e3
-    merged_ids = int(merged.max())
-    del merged
-  except Exception as e:  # pylint:disable=broad-except
-    print('merge skipped: %r' % (e,), file=sys.stderr)
+  if args.full:
+    try:
+      from ffn_amd import distributed as ffn_dist
+      seg = np.array(canvas._handle.read_segmentation())
+      seg[seg < 0] = 0
+      full = (world * shape[0], shape[1], shape[2])
+      boxes = ffn_dist.tile_volume(full, shape, (0, 0, 0))
+      barrier()
+      tm = time.perf_counter()
+      merged, _ = ffn_dist.merge_segmentations(
+          [(boxes[rank], seg)], full, rank, world,
+          device=coll_device)
+      barrier()
+      merge_ms = (time.perf_counter() - tm) * 1e3
+      merged_ids = int(merged.max())
+      del merged
+    except Exception as e:  # pylint:disable=broad-except
+      print('merge skipped: %r' % (e,), file=sys.stderr)
   canvas._flush_hot()
-  shader_ghz = sample_shader_clock(eng, 1)
-  board = board_under_stack(eng, 1) if rank == 0 else None
+  outputs = step_outputs(canvas, state) if args.dump_outputs and rank == 0 else None
+  shader_ghz = sample_shader_clock(eng, 1) if args.full else None
+  board = board_under_stack(eng, 1) if rank == 0 and args.full else None
   pace = {'ticks_10ns': eng.get_option('flow_pace_now'),
           'tuner_free_running_us': eng.get_option('flow_pace_free_ns') / 1e3,
           'tuner_at_its_beat_us': eng.get_option('flow_pace_best_ns') / 1e3,
@@ -815,6 +881,9 @@ def run_gpu(args, rank, local_rank, world):
   full_volume = None
   if not args.no_full_volume:
     full_volume = full_volume_pass(args, comm, model, exe, request, image, barrier)
+    full_seg = full_volume.pop('_segmentation')
+    if outputs is not None:
+      outputs['full_volume_segmentation_sample'] = volume_sample(full_seg)
   result = {
       'full_volume': full_volume,
       'shader_clock_ghz': shader_ghz,
@@ -889,6 +958,7 @@ def run_gpu(args, rank, local_rank, world):
       'model': model,
       'request': request,
       'image': image,
+      'outputs': outputs,
   }
   result = stream_totals(comm, result)
   if world > 1:
@@ -1371,6 +1441,17 @@ def build_parser():
                   help='native: ffn_canvas_segment_at runs each segment\'s FoV '
                   'loop inside the library; python: one ffn_canvas_step call '
                   'per step from the interpreter')
+  ap.add_argument('--full', action='store_true',
+                  help='also run everything beside the headline: the comparisons of the '
+                  'complete pass with the reference-minted runs and the second volume, '
+                  'the segmentation merge, shader clock and board samples, the CPU '
+                  'baseline with its GPU replay, the batched (configs[2]) and c5 '
+                  '(configs[4]) legs; the --no-* switches still drop single parts')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='stream mode: write what the timed path computed as DIR/<name>.npy '
+                  '(float32 / float64): the state of the canvas after the last timed '
+                  'step and the labels of the complete pass (seeded samples of the '
+                  'large volumes)')
   return ap
 
 
@@ -1390,6 +1471,8 @@ def main():
                      (args.gpus, world, args.gpus))
 
   if args.mode == 'sharded':
+    if args.dump_outputs:
+      raise SystemExit('--dump-outputs: the stream mode only')
     run_sharded(args, rank, local_rank, world)
     return
   res = run_gpu(args, rank, local_rank, world)
@@ -1397,6 +1480,11 @@ def main():
     return
 
   out = stream_line(args, world, res)
+  if args.dump_outputs:
+    write_outputs(args.dump_outputs, res['outputs'])
+  if not args.full:
+    print(json.dumps(out))
+    return
   if world == 1 and not args.no_cpu_baseline:
     oracle_trace, out['cpu_baseline'] = cpu_baseline(args)
     try:

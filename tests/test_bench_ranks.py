@@ -322,3 +322,47 @@ def test_self_launch_command(monkeypatch):
   monkeypatch.setenv('RANK', '0')
   with pytest.raises(SystemExit, match='--gpus 4 but WORLD_SIZE=2'):
     bench.main()
+
+
+def test_dump_outputs_and_full_switch(tmp_path):
+  """--dump-outputs: the state a caller holds after the last timed step (the seed
+  logits of the segment's box, NaN -> 0 with a mask; a seeded sample of the labels)
+  as f32 / f64 .npy files, the same sample on every call; --full is off by default."""
+  import bench
+  args = bench.build_parser().parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+  assert not args.full and args.dump_outputs is None
+  args = bench.build_parser().parse_args(['--full', '--dump-outputs', str(tmp_path)])
+  assert args.full and args.dump_outputs == str(tmp_path)
+
+  class Canvas:  # what step_outputs reads of a DeviceCanvas
+    shape = (80, 90, 100)
+    _pred_size = np.array([33, 33, 33])
+    _min_pos = np.array([20, 40, 50])
+    _max_pos = np.array([30, 70, 60])
+
+  rng = np.random.RandomState(5)
+  c = Canvas()
+  c.seed = rng.normal(size=c.shape).astype(np.float32)
+  c.seed[25, 50, 60] = np.nan
+  c.segmentation = rng.randint(0, 40, size=c.shape).astype(np.int32)
+  out = bench.step_outputs(c, {'prewarm_steps': 7, 'n': 4})
+  box = c.seed[4:47, 24:87, 34:77]  # min - 16 .. max + 16, clipped to the canvas
+  assert out['steps_seed_logits'].shape == box.shape
+  assert out['steps_seed_known'].sum() == box.size - 1
+  assert out['steps_seed_logits'][21, 26, 26] == 0
+  known = ~np.isnan(box)
+  assert np.array_equal(out['steps_seed_logits'][known], box[known])
+  assert list(out['steps_box_and_counts']) == [4, 24, 34, 47, 87, 77, 7, 4]
+  # (a volume smaller than the sample is written whole)
+  assert np.array_equal(out['steps_segmentation_sample'], c.segmentation.reshape(-1))
+  big = np.arange(300 ** 3, dtype=np.int32).reshape(300, 300, 300)
+  s1, s2 = bench.volume_sample(big), bench.volume_sample(big)
+  assert s1.dtype == np.float32 and s1.size == bench.DUMP_SAMPLE_VOXELS
+  assert np.array_equal(s1, s2)
+  assert np.array_equal(s1, big.reshape(-1)[s1.astype(np.int64)])
+  bench.write_outputs(str(tmp_path / 'd'), out)
+  for name, arr in out.items():
+    got = np.load(tmp_path / 'd' / (name + '.npy'))
+    assert got.dtype in (np.float32, np.float64) and np.array_equal(got, arr)
+  with pytest.raises(AssertionError):
+    bench.write_outputs(str(tmp_path / 'e'), {'labels': np.zeros(3, np.int32)})

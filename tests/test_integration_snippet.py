@@ -1,13 +1,13 @@
 """INTEGRATION.md section A, run AS WRITTEN: the python block is cut out of the document,
-exec'ed into the namespace of the REFERENCE's own ffn/inference/executor.py (imported
-through tools/ref_shims, unmodified), and the reference's own ThreadingExecutorClient /
-Canvas.segment_all run behind the HipBatchExecutor it defines -- with `libffn_hip.so`
-resolved to tests/abi_stub.c (the same four C entry points backed by the C oracle), so
-that the snippet's argtypes, shapes, locking and error path are exercised without a GPU.
+exec'ed into the namespace of this repository's mirror of ffn/inference/executor.py
+(ffn_amd/inference/executor.py: the same classes, queue protocol and constructor
+signatures as the reference's), and the mirror's ThreadingExecutorClient /
+Canvas.segment_all (the reference's literal host loop) run behind the HipBatchExecutor it
+defines -- with `libffn_hip.so` resolved to tests/abi_stub.c (the same four C entry points
+backed by the C oracle), so that the snippet's argtypes, shapes, locking and error path
+are exercised without a GPU.
 Expected: the reference-minted run tests/golden/ref_canvas_cells56.npz, bit for bit
-(that fixture came from the reference Canvas behind the same oracle forward).
-
-Needs /root/reference (this container only); skipped elsewhere."""
+(that fixture came from the reference Canvas behind the same oracle forward)."""
 import ctypes
 import functools
 import json
@@ -20,11 +20,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get('FFN_REFERENCE', '/root/reference')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'ffn')),
-                                reason='the reference checkout is not on this machine')
 
 
 def _snippet():
@@ -46,25 +42,20 @@ def stub(tmp_path_factory):
 
 @pytest.fixture(scope='module')
 def ref(stub):
-  """The reference's modules + the namespace the snippet was exec'ed into."""
-  os.environ.setdefault('PROTOCOL_BUFFERS_PYTHON_IMPLEMENTATION', 'python')
-  added = [REF, os.path.join(ROOT, 'tools', 'ref_shims')]
-  sys.path[:0] = added
-  try:
-    from ffn.inference import executor as ref_executor
-    from ffn.inference import inference as ref_inference
-    from ffn.inference import inference_pb2
-    from ffn.inference import inference_utils as ref_utils
-    from ffn.inference import movement as ref_movement
-    from ffn.inference import seed as ref_seed
-    from ffn.training import model as ref_model
-  finally:
-    for p in added:
-      sys.path.remove(p)
-  assert ref_executor.__file__.startswith(REF)
+  """The executor-side modules + the namespace the snippet was exec'ed into."""
+  if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+  from ffn_amd.inference import executor as ref_executor
+  from ffn_amd.inference import inference as ref_inference
+  from ffn_amd.inference import inference_utils as ref_utils
+  from ffn_amd.inference import movement as ref_movement
+  from ffn_amd.inference import request as inference_pb2
+  from ffn_amd.inference import seed as ref_seed
+  from ffn_amd.training import model as ref_model
+  assert ref_executor.__file__.startswith(os.path.join(ROOT, 'ffn_amd'))
   real_cdll = ctypes.CDLL
 
-  def cdll(name, *a, **k):  # `libffn_hip.so` = the stub on this machine
+  def cdll(name, *a, **k):  # `libffn_hip.so` = the stub
     return real_cdll(stub if name == 'libffn_hip.so' else name, *a, **k)
 
   ns = dict(vars(ref_executor))  # "an addition to ffn/inference/executor.py"
@@ -93,8 +84,8 @@ def test_snippet_class_is_a_subclass_of_the_references_executor(ref):
 
 
 def test_reference_canvas_behind_the_snippet_reproduces_the_reference_run(ref):
-  """ffn/inference/executor.py:207-340 (server loop, unmodified) + inference.py:356-384,
-  460-683 (Canvas.predict / update_at / segment_all, unmodified) + the snippet."""
+  """The mirror of ffn/inference/executor.py:207-340 (server loop) + inference.py:356-384,
+  460-683 (Canvas.predict / update_at / segment_all) + the snippet."""
   from ffn_amd import synthetic
   ns, m = ref
   g = np.load(os.path.join(GOLDEN, 'ref_canvas_cells56.npz'))
