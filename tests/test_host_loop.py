@@ -547,3 +547,81 @@ def test_non_default_inference_options(shim, fib25_blob, name, native):
   assert c._native_loop_ok() == native
   option_cases.run(c, g)
   option_cases.check(c, g, steps=c._handle.steps_seen if native else None)
+
+
+# the oracle forwards of the batch-16 cases, keyed on their exact inputs
+_FORWARD_MEMO = {}
+
+
+@pytest.fixture
+def memo_forward(monkeypatch):
+  """The batch-16 cases step many canvases of the same two fixture volumes: the
+  emulated device's oracle forward is memoised on its exact inputs (equal
+  inputs, equal logits -- a cache, not an approximation)."""
+  import hashlib
+  from tests import emulated_device
+  inner = emulated_device.ffn_oracle.forward
+
+  def forward(image, seed, blob, depth, *args, **kwargs):
+    if args or kwargs:
+      return inner(image, seed, blob, depth, *args, **kwargs)
+    image = np.ascontiguousarray(image, np.float32)
+    seed = np.ascontiguousarray(seed, np.float32)
+    key = (hashlib.sha1(image.tobytes()).digest(), hashlib.sha1(seed.tobytes()).digest(),
+           image.shape, hashlib.sha1(np.ascontiguousarray(blob).tobytes()).digest(),
+           depth)
+    if key not in _FORWARD_MEMO:
+      _FORWARD_MEMO[key] = inner(image, seed, blob, depth)
+    return _FORWARD_MEMO[key].copy()
+
+  monkeypatch.setattr(emulated_device.ffn_oracle, 'forward', forward)
+
+
+@pytest.mark.parametrize('groups,carry,fail_round,fail_code', [
+    (1, True, None, _lib.ERR_RANGE), (2, False, None, _lib.ERR_RANGE),
+    (1, True, 0, _lib.ERR_RANGE), (1, False, 0, _lib.ERR_FLOW)])
+def test_segment_many_at_batch_16(shim, fib25_blob, memo_forward, groups, carry,
+                                  fail_round, fail_code):
+  """ffn_host::segment_many at the benchmark's batch (16 canvases per engine
+  call; bench.py's batched leg): 18 canvases of the reference-minted runs
+  under MultiCanvasDriver(batch_size=16), with one group or two groups in two
+  threads, with and without the carried step, and with a FULL round of 16
+  voided once (FFN_ERR_RANGE / FFN_ERR_FLOW) and the call resumed.  Every canvas
+  repeats the reference's own run step for step: the loop's per-canvas
+  bookkeeping (request slots, results, finished flags, resumes) holds at 16."""
+  import json
+  names = ['cells72', 'cells72', 'cells56'] * 6
+  client, engine, canvases, gold = _many_canvases(shim, fib25_blob, names)
+  engine.max_batch = 16
+  engine.fail_round = fail_round
+  engine.fail_code = fail_code
+  drv = inference.MultiCanvasDriver(engine, batch_size=16, native=True,
+                                    groups=groups, carry=carry)
+  assert drv.native and drv.groups == groups
+  done = []
+  drv.run(((c, functools.partial(seed_lib.PolicyFixed, coords=gold[n]['seeds']))
+           for c, n in zip(canvases, names)), on_done=done.append)
+  assert sorted(id(c) for c in done) == sorted(id(c) for c in canvases)
+  total = 0
+  for c, n in zip(canvases, names):
+    g = gold[n]
+    assert np.array_equal(np.array(c._handle.steps_seen).reshape(-1, 3), g['steps']), n
+    assert np.array_equal(np.asarray(c.segmentation), g['segmentation']), n
+    ref = json.loads(str(g['counters']))
+    for key in ('update_at-calls', 'voxels-segmented', 'skip_invalid_pos',
+                'skip_threshold', 'seed_got_too_weak', 'segment_at-loop-calls'):
+      if key in ref:
+        assert c.counters[key].value == ref[key], (n, key)
+    total += len(g['steps'])
+  assert drv.steps == total
+  assert max(engine.batch_sizes) <= 16 and engine.rounds < total
+  if groups == 1:
+    assert max(engine.batch_sizes) == 16
+  voided = 0 if fail_round is None else 1
+  if voided:
+    # the voided round was a full one, and was repeated as one
+    assert engine.batch_sizes[fail_round] == 16, engine.batch_sizes[:8]
+  assert engine.range_fallbacks == (voided if fail_code == _lib.ERR_RANGE else 0)
+  assert engine.flow_fallbacks == (voided if fail_code == _lib.ERR_FLOW else 0)
+  assert (engine.carried > 0) == (carry and groups == 1)
+  assert not shim.shim_carry_active()
