@@ -204,6 +204,11 @@ SIGNATURES = {
                                       ctypes.c_int32]),
     'ffn_canvas_segment_turn': (_I, [_P, _P, _P, _P, ctypes.c_int32, _P, _P, _P, _P,
                                      _P]),
+    'ffn_canvas_set_restrictor': (_I, [_P, _P, _P, _P, _I3, _I3, _I3,
+                                       ctypes.c_int32]),
+    'ffn_canvas_read_restriction': (_I, [_P, _I3, _I3, _P]),
+    'ffn_canvas_take_restricted_skips': (_I, [_P,
+                                              ctypes.POINTER(ctypes.c_int64)]),
     'ffn_canvas_read_seed': (_I, [_P, _I3, _I3, _P]),
     'ffn_canvas_read_segmentation': (_I, [_P, _I3, _I3, _P]),
     'ffn_canvas_write_seed': (_I, [_P, _I3, _I3, _P]),

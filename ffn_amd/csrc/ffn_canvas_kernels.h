@@ -157,7 +157,8 @@ struct TurnRecord {
   int chosen;                    // index of the next seed in the candidate list, -1 none
   int pad[2];
 };
-constexpr int kTurnOk = 0, kTurnSegmented = 1, kTurnTooClose = 2, kTurnNotReached = 3;
+constexpr int kTurnOk = 0, kTurnSegmented = 1, kTurnTooClose = 2, kTurnNotReached = 3,
+              kTurnRestricted = 4;
 
 // mark_mode 0: no marker; 1: seg[mark] = -1 if it is 0 (inference.py:600-603, a
 // seed that got too weak); 2: the same, but only when nothing is committed
@@ -183,20 +184,31 @@ __global__ void turn_commit_kernel(const float* __restrict__ seed,
 }
 
 // one wavefront per candidate: segmentation[pos] > 0 (Canvas.is_valid_pos,
-// inference.py:341), else any id > 0 in the clipped box pos +- min_boundary_dist
-// (inference.py:575-581)
+// inference.py:341), else a restrictor veto (MovementRestrictor.is_valid_pos /
+// is_valid_seed, inference.py:573-574: the reference moves on before the
+// too-close test, so no marker), else any id > 0 in the clipped box
+// pos +- min_boundary_dist (inference.py:575-581).  rplanes: the canvas'
+// restriction bit planes (ffn_restrict_kernels.h), NULL without a restrictor.
 __global__ __launch_bounds__(64) void turn_eval_kernel(
     const float* __restrict__ seed, const int32_t* __restrict__ seg, int cz, int cy,
     int cx, const int32_t* __restrict__ cand, int mz, int my, int mx,
     int* __restrict__ flags, float* __restrict__ cand_seed,
-    int32_t* __restrict__ cand_seg) {
+    int32_t* __restrict__ cand_seg, const unsigned long long* __restrict__ rplanes,
+    size_t plane_words, int row_words) {
   const int j = blockIdx.x;
   const int z = cand[3 * j], y = cand[3 * j + 1], x = cand[3 * j + 2];
   const size_t ci = ((size_t)z * cy + y) * cx + x;
   const int32_t s = seg[ci];
   int flag = kTurnOk;
+  bool restricted = false;
+  if (rplanes) {
+    const size_t wi = ((size_t)z * cy + y) * row_words + (x >> 6);
+    restricted = ((rplanes[wi] | rplanes[plane_words + wi]) >> (x & 63)) & 1ull;
+  }
   if (s > 0) {
     flag = kTurnSegmented;
+  } else if (restricted) {
+    flag = kTurnRestricted;
   } else {
     const int z0 = max(z - mz, 0), z1 = min(z + mz + 1, cz);
     const int y0 = max(y - my, 0), y1 = min(y + my + 1, cy);

@@ -22,6 +22,7 @@
 
 #include "ffn_internal.h"
 #include "ffn_kernels.h"
+#include "ffn_restrict_kernels.h"
 #include "ffn_host_loop.h"
 
 using namespace ffn;
@@ -332,6 +333,13 @@ struct ffn_canvas {
   int hint_n = 0;
   int hint_pos[kSpecMax][3] = {};
   bool hint_from_loop = false;  // the next step is the segment loop's own
+  // MovementRestrictor (ffn_canvas_set_restrictor): [pos plane][seed plane] of
+  // restrict_plane_words 64-bit words each (ffn_restrict_kernels.h); NULL: none.
+  // The host loop reads its copy of the pos plane (restrict_host).
+  unsigned long long* restrict_planes = nullptr;
+  size_t restrict_plane_words = 0;
+  int restrict_row_words = 0;
+  std::vector<uint64_t> restrict_host;
 
   void mark_dirty(const int lo[3], const int hi[3]) {
     const int dims[3] = {cz, cy, cx};
@@ -1734,6 +1742,8 @@ void ffn_engine_destroy(ffn_engine* e) {
     (void)hipFree(c->image_lut);
     (void)hipFree(c->seed);
     (void)hipFree(c->seg);
+    (void)hipFree(c->restrict_planes);
+    c->restrict_planes = nullptr;
     if (c->ev_util) (void)hipEventDestroy(c->ev_util);
     c->ev_util = nullptr;
     c->image = c->seed = nullptr;
@@ -2591,6 +2601,7 @@ void ffn_canvas_destroy(ffn_canvas* c) {
     (void)hipFree(c->image_lut);
     (void)hipFree(c->seed);
     (void)hipFree(c->seg);
+    (void)hipFree(c->restrict_planes);
   }
   delete c;
 }
@@ -3191,6 +3202,157 @@ int ffn_canvas_segment_history(ffn_canvas* c, size_t first, size_t n,
   return FFN_OK;
 }
 
+int ffn_canvas_set_restrictor(ffn_canvas* c, const uint8_t* mask,
+                              const uint8_t* seed_mask, const uint8_t* shift_mask,
+                              const int32_t shift_shape[3], const int32_t pre[3],
+                              const int32_t post[3], int32_t scale) {
+  if (!c) return fail(FFN_ERR_ARG, "null canvas");
+  ffn_engine* e = c->engine;
+  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
+  if (shift_mask) {
+    if (!shift_shape || !pre || !post)
+      return fail(FFN_ERR_ARG, "shift mask without its shape / FoV offsets");
+    for (int k = 0; k < 3; ++k) {
+      if (shift_shape[k] < 1) return fail(FFN_ERR_ARG, "bad shift mask shape");
+      // (post >= -1: every numpy stop of is_valid_pos is >= 0 at a position >= 0)
+      if (post[k] < -1) return fail(FFN_ERR_ARG, "shift mask FoV ends before 0");
+    }
+    if (scale < 1) return fail(FFN_ERR_ARG, "shift mask scale must be >= 1");
+  }
+  if (int rc = resolve_many_carry(e, c)) return rc;
+  UtilLock lock_(e);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(lock_.begin(e, c));
+  // the old planes: no turn queued on the utility stream may still read them
+  HIP_TRY(hipStreamSynchronize(e->ustream));
+  (void)hipFree(c->restrict_planes);
+  c->restrict_planes = nullptr;
+  c->restrict_plane_words = 0;
+  c->restrict_row_words = 0;
+  std::vector<uint64_t>().swap(c->restrict_host);
+  c->loop.restrict_bits = nullptr;
+  if (!mask && !seed_mask && !shift_mask) return FFN_OK;  // cleared
+
+  const int Z = c->cz, Y = c->cy, X = c->cx;
+  const int W = (X + 63) / 64;
+  const size_t pw = (size_t)Z * Y * W;
+  const size_t wave_blocks = std::min<size_t>((pw + 3) / 4, 8192);  // 4 waves / block
+  unsigned long long* planes = nullptr;
+  uint8_t* d_src = nullptr;
+  unsigned long long *d_ax = nullptr, *d_ay = nullptr;
+  hipError_t err = hipMalloc(&planes, 2 * pw * sizeof(uint64_t));
+  // mask -> pos plane, seed mask -> seed plane: one u8 temporary at a time
+  const uint8_t* srcs[2] = {mask, seed_mask};
+  for (int k = 0; k < 2 && err == hipSuccess; ++k) {
+    unsigned long long* plane = planes + k * pw;
+    if (!srcs[k]) {
+      err = hipMemsetAsync(plane, 0, pw * sizeof(uint64_t), e->ustream);
+      continue;
+    }
+    err = hipMalloc(&d_src, c->nvox);
+    if (err == hipSuccess) err = hipMemcpy(d_src, srcs[k], c->nvox, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+      hipLaunchKernelGGL(restrict_pack_kernel, dim3((unsigned)wave_blocks), dim3(256), 0,
+                         e->ustream, d_src, (long)Z * Y, X, W, plane);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
+    (void)hipFree(d_src);
+    d_src = nullptr;
+  }
+  if (shift_mask && err == hipSuccess) {
+    const int Zs = shift_shape[0], Ys = shift_shape[1], Xs = shift_shape[2];
+    const size_t ns = (size_t)Zs * Ys * Xs;
+    const size_t nax = (size_t)Zs * Ys * W, nay = (size_t)Zs * Y * W;
+    err = hipMalloc(&d_src, ns);
+    if (err == hipSuccess) err = hipMalloc(&d_ax, nax * sizeof(uint64_t));
+    if (err == hipSuccess) err = hipMalloc(&d_ay, nay * sizeof(uint64_t));
+    if (err == hipSuccess) err = hipMemcpy(d_src, shift_mask, ns, hipMemcpyHostToDevice);
+    if (err == hipSuccess) {
+      hipLaunchKernelGGL(restrict_shift_x_kernel,
+                         dim3((unsigned)std::min<size_t>((nax + 3) / 4, 8192)), dim3(256),
+                         0, e->ustream, d_src, (long)Zs * Ys, Xs, X, W, pre[2], post[2],
+                         scale, d_ax);
+      hipLaunchKernelGGL(restrict_shift_y_kernel, dim3(grid_for((long)nay)), dim3(256), 0,
+                         e->ustream, d_ax, Zs, Ys, Y, W, pre[1], post[1], scale, d_ay);
+      hipLaunchKernelGGL(restrict_shift_z_kernel, dim3(grid_for((long)pw)), dim3(256), 0,
+                         e->ustream, d_ay, Zs, Z, Y, W, pre[0], post[0], planes);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
+    (void)hipFree(d_src);
+    (void)hipFree(d_ax);
+    (void)hipFree(d_ay);
+    d_src = nullptr;
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
+  // the host loop's copy of the pos plane (1 bit / voxel)
+  if (err == hipSuccess) {
+    try {
+      c->restrict_host.resize(pw);
+    } catch (const std::bad_alloc&) {
+      (void)hipFree(planes);
+      return fail(FFN_ERR_ARG, "no host memory for the restriction plane");
+    }
+    err = hipMemcpy(c->restrict_host.data(), planes, pw * sizeof(uint64_t),
+                    hipMemcpyDeviceToHost);
+  }
+  if (err != hipSuccess) {
+    (void)hipFree(planes);
+    std::vector<uint64_t>().swap(c->restrict_host);
+    return fail(FFN_ERR_HIP, "restriction planes: %s", hipGetErrorString(err));
+  }
+  c->restrict_planes = planes;
+  c->restrict_plane_words = pw;
+  c->restrict_row_words = W;
+  c->loop.restrict_bits = c->restrict_host.data();
+  c->loop.restrict_dims[0] = Z;
+  c->loop.restrict_dims[1] = Y;
+  c->loop.restrict_dims[2] = X;
+  c->loop.restrict_row_words = W;
+  return FFN_OK;
+}
+
+int ffn_canvas_read_restriction(ffn_canvas* c, const int32_t lo[3],
+                                const int32_t hi[3], uint8_t* dst) {
+  UtilLock lock_(c ? c->engine : nullptr);
+  if (int rc = check_canvas(c)) return rc;
+  if (!lo || !hi || !dst) return fail(FFN_ERR_ARG, "null argument");
+  if (int rc = check_box(c, lo, hi)) return rc;
+  long total = 0;
+  const Box b = make_box(c, lo, hi, &total);
+  if (total <= 0) return FFN_OK;
+  if (!c->restrict_planes) {  // no restrictor: nothing is blocked
+    std::memset(dst, 0, (size_t)total);
+    return FFN_OK;
+  }
+  ffn_engine* e = c->engine;
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(lock_.begin(e, c, true));
+  uint8_t* d_out = nullptr;
+  HIP_TRY(hipMalloc(&d_out, (size_t)total));
+  hipLaunchKernelGGL(restrict_read_kernel, dim3(grid_for(total)), dim3(256), 0,
+                     e->ustream, c->restrict_planes, c->restrict_plane_words, c->cy,
+                     c->restrict_row_words, b.lo[0], b.lo[1], b.lo[2], b.n[1], b.n[2],
+                     total, d_out);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
+  if (err == hipSuccess) err = hipMemcpy(dst, d_out, (size_t)total, hipMemcpyDeviceToHost);
+  (void)hipFree(d_out);
+  if (err != hipSuccess)
+    return fail(FFN_ERR_HIP, "read_restriction: %s", hipGetErrorString(err));
+  return FFN_OK;
+}
+
+int ffn_canvas_take_restricted_skips(ffn_canvas* c, int64_t* out) {
+  if (!c || !out) return fail(FFN_ERR_ARG, "null argument");
+  if (c->engine)
+    if (int rc = resolve_many_carry(c->engine, c)) return rc;
+  *out = c->loop.skip_restricted;
+  c->loop.skip_restricted = 0;
+  return FFN_OK;
+}
+
 int ffn_canvas_read_points(ffn_canvas* c, int n, const int32_t* pos,
                            float* seed_out, int32_t* seg_out) {
   UtilLock lock_(c ? c->engine : nullptr);
@@ -3441,7 +3603,8 @@ int ffn_canvas_segment_turn(ffn_canvas* c, const ffn_turn_request* rq,
     hipLaunchKernelGGL(turn_eval_kernel, dim3(n), dim3(64), 0, e->ustream, c->seed,
                        c->seg, c->cz, c->cy, c->cx, d_cand, rq->min_boundary_dist[0],
                        rq->min_boundary_dist[1], rq->min_boundary_dist[2], d_flag,
-                       d_cseed, d_cseg);
+                       d_cseed, d_cseg, c->restrict_planes, c->restrict_plane_words,
+                       c->restrict_row_words);
     hipLaunchKernelGGL(turn_pick_kernel, dim3(1), dim3(64), 0, e->ustream, c->seg,
                        c->cy, c->cx, d_cand, n, d_flag, d_rec);
     if (rq->do_init) {

@@ -77,6 +77,27 @@ struct SegmentState {
   // segment_many: tallies since the segment's start, over all the calls it took
   int64_t many_steps = 0, many_skip_threshold = 0, many_skip_invalid_pos = 0,
           many_gate_rejects = 0;
+  // MovementRestrictor.is_valid_pos (movement.py:315-336) as a bit plane: bit
+  // x % 64 of word (z * dims[1] + y) * row_words + x / 64 set = the FoV may not
+  // move there (ffn_canvas_set_restrictor; the layout of ffn_restrict_kernels.h).
+  // NULL: no restrictor.
+  const uint64_t* restrict_bits = nullptr;
+  int32_t restrict_dims[3] = {0, 0, 0};
+  int64_t restrict_row_words = 0;
+  // positions popped and then vetoed by the restrictor ("skip_restriced_pos"),
+  // over every loop since the tally was last taken
+  int64_t skip_restricted = 0;
+
+  bool pos_blocked(const Coord& c) const {
+    if (!restrict_bits) return false;
+    if (c.z < 0 || c.y < 0 || c.x < 0 || c.z >= restrict_dims[0] ||
+        c.y >= restrict_dims[1] || c.x >= restrict_dims[2])
+      return false;
+    const uint64_t w =
+        restrict_bits[((int64_t)c.z * restrict_dims[1] + c.y) * restrict_row_words +
+                      (c.x >> 6)];
+    return (w >> (c.x & 63)) & 1u;
+  }
 };
 
 constexpr int kHintMax = 3;  // positions per Dev::hint_next call
@@ -184,36 +205,44 @@ class SegmentLoop {
       return FFN_OK;
     }
     Coord pos;
-    if (st_.has_pending) {
-      pos = st_.pending;
-    } else {
-      bool found = false;
-      const int rc = next(&pos, &found, out);
-      if (rc) return rc;
-      if (!found) {
+    for (;;) {
+      if (st_.has_pending) {
+        pos = st_.pending;
+      } else {
+        bool found = false;
+        const int rc = next(&pos, &found, out);
+        if (rc) return rc;
+        if (!found) {
+          st_.active = false;
+          *ended = true;
+          return FFN_OK;
+        }
+      }
+      // "seed got too weak" (inference.py:503-505)
+      if (!st_.start_logit_known) {
+        int32_t seg;
+        const int32_t sp[3] = {st_.start.z, st_.start.y, st_.start.x};
+        const int rc = dev_.read_point(sp, &st_.start_logit, &seg);
+        if (rc) {
+          st_.pending = pos;
+          st_.has_pending = true;
+          return rc;
+        }
+        st_.start_logit_known = true;
+      }
+      if (st_.start_logit < p_.step.move_threshold) {
+        out->seed_got_too_weak = 1;
+        st_.has_pending = false;
         st_.active = false;
         *ended = true;
         return FFN_OK;
       }
-    }
-    // "seed got too weak" (inference.py:503-505)
-    if (!st_.start_logit_known) {
-      int32_t seg;
-      const int32_t sp[3] = {st_.start.z, st_.start.y, st_.start.x};
-      const int rc = dev_.read_point(sp, &st_.start_logit, &seg);
-      if (rc) {
-        st_.pending = pos;
-        st_.has_pending = true;
-        return rc;
-      }
-      st_.start_logit_known = true;
-    }
-    if (st_.start_logit < p_.step.move_threshold) {
-      out->seed_got_too_weak = 1;
+      // the restrictor's veto (inference.py:506-508): the reference `continue`s
+      // before update_at, so the position is not marked visited and may be
+      // queued, popped and skipped again
+      if (!st_.pos_blocked(pos)) break;
+      ++st_.skip_restricted;
       st_.has_pending = false;
-      st_.active = false;
-      *ended = true;
-      return FFN_OK;
     }
     // ---- one FoV step ----------------------------------------------------------
     pd->pos = pos;
@@ -357,7 +386,8 @@ class SegmentLoop {
 
   // The first kHintMax queued positions that next() can still accept once the
   // step at `cur` has been made: not visited (`cur` counts as visited by then),
-  // FoV inside the canvas.  Which of them is valid depends on the step's result;
+  // FoV inside the canvas, not vetoed by the restrictor (prepare() skips those,
+  // the device's choice among the hints must be what it pops).  Which of them is valid depends on the step's result;
   // next() takes the first that is, moves queued by the step come after them.
   // ... and not KNOWN to stay invalid: the values the last step's record brought for the
   // head of the queue (and the moves it queued) still hold where the step at `cur` cannot
@@ -370,7 +400,9 @@ class SegmentLoop {
     int n = 0;
     for (const auto& e : st_.queue) {
       if (n >= kHintMax) break;
-      if (e.q == qc || st_.done.count(e.q) || !in_bounds(e.pos)) continue;
+      if (e.q == qc || st_.done.count(e.q) || !in_bounds(e.pos) ||
+          st_.pos_blocked(e.pos))
+        continue;
       const auto it = st_.cache.find(e.pos);
       if (it != st_.cache.end()) {
         const float seed = it->second.first;

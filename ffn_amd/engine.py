@@ -611,6 +611,43 @@ class DeviceCanvasHandle:
             cnts[:k].copy(), bool(res.committed), int(res.chosen), flags[:n],
             cseed[:n], cseg[:n])
 
+  def set_restrictor(self, mask=None, seed_mask=None, shift_mask=None,
+                     pre=(0, 0, 0), post=(0, 0, 0), scale=1):
+    """ffn_canvas_set_restrictor: MovementRestrictor's vetoes as device bit
+    planes.  mask / seed_mask: canvas-shaped, shift_mask: the reduced 3-d mask;
+    non-zero = set (numpy truthiness).  pre / post: zyx shift-mask FoV start and
+    end - 1.  Nothing given: the restrictor is cleared.  The arrays are copied."""
+    def u8(a, shape=None):
+      if a is None:
+        return None
+      a = np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+      if shape is not None and a.shape != tuple(shape):
+        raise ValueError('restrictor volume of shape %r on a canvas of %r' %
+                         (a.shape, tuple(shape)))
+      return a
+    m, sm, sh = u8(mask, self.shape), u8(seed_mask, self.shape), u8(shift_mask)
+    if sh is not None and sh.ndim != 3:
+      raise ValueError('the reduced shift mask must be 3-d')
+    ptr = lambda a: None if a is None else a.ctypes.data
+    check(self._lib.ffn_canvas_set_restrictor(
+        self._h, ptr(m), ptr(sm), ptr(sh), i3(sh.shape if sh is not None else (0, 0, 0)),
+        i3(pre), i3(post), int(scale)))
+
+  def read_restriction(self, lo=None, hi=None) -> np.ndarray:
+    """uint8 [hi - lo]: bit 0 pos_blocked, bit 1 seed_blocked."""
+    lo, hi, shp = self._box(lo or (0, 0, 0), hi or self.shape)
+    out = np.empty(shp, np.uint8)
+    check(self._lib.ffn_canvas_read_restriction(self._h, i3(lo), i3(hi),
+                                                out.ctypes.data))
+    return out
+
+  def take_restricted_skips(self) -> int:
+    """Positions the library's segment loops skipped for the restrictor since
+    the last call (the reference's skip_restriced_pos)."""
+    out = ctypes.c_int64(0)
+    check(self._lib.ffn_canvas_take_restricted_skips(self._h, ctypes.byref(out)))
+    return int(out.value)
+
   def _box(self, lo, hi):
     lo = [int(v) for v in lo]
     hi = [int(v) for v in hi]

@@ -681,6 +681,30 @@ _STEP_RESULT = struct.Struct('<6f6i6ifIi16f16iIi')
 assert _STEP_RESULT.size == ctypes.sizeof(_lib.StepResult)
 
 
+def _device_restriction(restrictor, shape):
+  """What `ffn_canvas_set_restrictor` takes for `restrictor`, or None if the
+  device cannot stand in for it: only a stock `movement.MovementRestrictor`
+  (not a subclass) whose mask / seed mask have the canvas shape, whose reduced
+  shift mask is 3-d and whose shift-mask FoV ends at >= 0 on every axis (then
+  no numpy stop of `is_valid_pos` is negative at a position in the canvas)."""
+  if type(restrictor) is not movement.MovementRestrictor:
+    return None
+  out = {'mask': restrictor.mask, 'seed_mask': restrictor.seed_mask,
+         'shift_mask': restrictor.shift_mask}
+  for key in ('mask', 'seed_mask'):
+    if out[key] is not None and tuple(np.shape(out[key])) != tuple(shape):
+      return None
+  if out['shift_mask'] is not None:
+    scale = restrictor._shift_mask_scale
+    pre = [int(v) for v in restrictor._shift_mask_fov_pre_offset]
+    post = [int(v) for v in restrictor._shift_mask_fov_post_offset]
+    if (np.ndim(out['shift_mask']) != 3 or len(pre) != 3 or len(post) != 3 or
+        min(post) < -1 or int(scale) != scale or scale < 1):
+      return None
+    out.update(pre=pre, post=post, scale=int(scale))
+  return out
+
+
 class DeviceCanvas(Canvas):
   """Canvas whose image / seed / segmentation live in HBM for its lifetime."""
 
@@ -728,6 +752,53 @@ class DeviceCanvas(Canvas):
     self._pred_size_t = tuple(int(v) for v in self._pred_size)
     self._fast_policy = (
         type(self.movement_policy) is movement.FaceMaxMovementPolicy)
+    self._upload_restrictor()
+
+  # -- the restrictor on the device ------------------------------------------------------
+  @property
+  def restrictor(self):
+    return self.__dict__.get('_restrictor')
+
+  @restrictor.setter
+  def restrictor(self, value):
+    self.__dict__['_restrictor'] = value
+    if self.__dict__.get('_handle') is not None:
+      self._upload_restrictor()
+
+  def refresh_restrictor(self):
+    """Uploads the restrictor's arrays again.  The device (the library's segment
+    loop and turn) tests a SNAPSHOT of them, taken when the canvas was made or
+    `restrictor` last assigned: call this after editing them in place."""
+    self._upload_restrictor()
+
+  def _upload_restrictor(self):
+    """`ffn_canvas_set_restrictor` for an eligible restrictor
+    (`_device_restriction`): the library's loop and turn then apply it
+    themselves.  Any other restrictor keeps the Python loop."""
+    self.__dict__.pop('_native_ok', None)
+    self.__dict__.pop('_turn_static', None)
+    self._invalidate_cache()
+    handle = self._handle
+    was_on = self.__dict__.get('_restrict_on', False)
+    self._restrict_on = False
+    args = (_device_restriction(self.restrictor, self.shape)
+            if hasattr(handle, 'set_restrictor') else None)
+    if args is None or all(args[k] is None
+                           for k in ('mask', 'seed_mask', 'shift_mask')):
+      if was_on:
+        self._call(handle.set_restrictor)  # (clears it)
+      return
+    t0 = time.perf_counter()
+    self._call(handle.set_restrictor, **args)
+    #: seconds the last upload of the restrictor took (build of the bit planes)
+    self.restrictor_upload_seconds = time.perf_counter() - t0
+    self._restrict_on = True
+
+  def _restrictor_ok(self) -> bool:
+    """The library may run this canvas' loop / turn as far as the restrictor
+    goes: none to apply, or one that the device applies itself."""
+    return bool(getattr(self.restrictor, 'is_trivial', self.restrictor is None) or
+                self.__dict__.get('_restrict_on', False))
 
   def _alloc_state(self, storage_cls):
     del storage_cls
@@ -774,13 +845,13 @@ class DeviceCanvas(Canvas):
   def _turn_ok(self) -> bool:
     """True if `ffn_canvas_segment_turn` may answer the seed loop's questions
     (inference.py:573-660) ahead of time: nothing between two segments that the
-    device does not see -- no restrictor masks, no timed checkpoint about to
-    be taken, no probability map, the stock validity test."""
+    device does not see -- no restrictor masks it has not been given, no timed
+    checkpoint about to be taken, no probability map, the stock validity
+    test."""
     ok = self.__dict__.get('_turn_static')
     if ok is None:
       ok = (hasattr(self._handle, 'segment_turn') and
-            not self.keep_probability_maps and
-            getattr(self.restrictor, 'is_trivial', self.restrictor is None))
+            not self.keep_probability_maps and self._restrictor_ok())
       self._turn_static = ok
     # A timed checkpoint is taken BETWEEN the loop's questions, and a turn moves
     # the canvas past them (the next seed initialised, too-close seeds marked).
@@ -850,6 +921,8 @@ class DeviceCanvas(Canvas):
       f = int(flags[k])
       if f == 3:  # after the chosen one: not looked at
         break
+      # (4: vetoed by the restrictor on the device; its point values answer
+      # is_valid_pos, then the host restrictor says no, as in the reference)
       seen[c] = f
       self._cache[c] = (float(cseed[k]), -1 if f == 2 else int(cseg[k]))
     # the -1 marker was written in mode 1 always, in mode 2 (commit) only when
@@ -1025,7 +1098,7 @@ class DeviceCanvas(Canvas):
             hasattr(self._handle, 'segment_at') and
             getattr(self._exec_client, 'in_thread', False) and
             type(self.movement_policy) is movement.FaceMaxMovementPolicy and
-            getattr(self.restrictor, 'is_trivial', self.restrictor is None) and
+            self._restrictor_ok() and
             cls._segment_at_gen is DeviceCanvas._segment_at_gen)
       self._native_ok = ok
     # hooks may also be set on the instance (canvas.update_at = ...)
@@ -1118,6 +1191,10 @@ class DeviceCanvas(Canvas):
       c['skip_invalid_pos'].IncrementBy(int(res.skip_invalid_pos))
     if res.seed_got_too_weak:
       c['seed_got_too_weak'].Increment()
+    if self.__dict__.get('_restrict_on', False):
+      skipped = self._call(self._handle.take_restricted_skips)
+      if skipped:
+        c['skip_restriced_pos'].IncrementBy(skipped)
     self.gate_rejects += int(res.gate_rejects)
     self._min_pos = np.array([int(v) for v in res.min_pos])
     self._max_pos = np.array([int(v) for v in res.max_pos])

@@ -296,8 +296,9 @@ int ffn_canvas_commit_assign(ffn_canvas* canvas, const int32_t lo[3],
  *   4. do_init: Canvas.init_seed(candidates[chosen], init_value)
  *      (inference.py:282-286) when there is one.
  * cand_flags[k]: 0 passed (k = chosen), 1 already segmented, 2 too close (marked),
- * 3 after the chosen one (untouched); cand_seed / cand_seg: the canvas values at
- * candidate k as step 3 saw them. */
+ * 3 after the chosen one (untouched), 4 vetoed by the canvas' restrictor
+ * (ffn_canvas_set_restrictor, not marked); cand_seed / cand_seg: the canvas
+ * values at candidate k as step 3 saw them. */
 typedef struct ffn_turn_request {
   int32_t do_commit;
   int32_t lo[3], hi[3];
@@ -325,6 +326,40 @@ int ffn_canvas_segment_turn(ffn_canvas* canvas, const ffn_turn_request* request,
                             int32_t* overlap_ids, int64_t* overlap_counts,
                             int32_t* cand_flags, float* cand_seed,
                             int32_t* cand_seg);
+
+/* MovementRestrictor (movement.py:247-336) on the canvas.  Two bits per voxel p:
+ *   pos_blocked(p)  = mask[p] != 0, or any non-zero voxel of shift_mask (the
+ *                     REDUCED, thresholded mask, [Zs][Ys][Xs]) in the box
+ *                     z: max(z+pre[0], 0) .. min(z+post[0], Zs-1)   (unscaled),
+ *                     y: max(y+pre[1], 0) // scale .. min((y+post[1]) // scale, Ys-1),
+ *                     x: the same with pre[2] / post[2] / Xs
+ *                     (// = floor division; an empty range: not blocked);
+ *   seed_blocked(p) = seed_mask[p] != 0.
+ * pre / post (zyx) are the restrictor's shift-mask FoV start and end - 1; post
+ * must be >= -1 on every axis.  mask / seed_mask are uint8 volumes of the canvas
+ * shape, any of the three may be NULL; all three NULL clears the restrictor.  The
+ * arrays are read during the call (a snapshot: later edits of the caller's copy
+ * are not seen).  The device keeps both bits as planes of 64 voxels per word
+ * along x (<= 2 bits / voxel), the host loop a copy of pos_blocked (1 bit).
+ * With a restrictor
+ *   - the segment loop (ffn_canvas_segment_at / _segment_many) skips a popped
+ *     position that is pos_blocked after the seed-too-weak test, without marking
+ *     it visited (inference.py:506-508), and tallies it (below); its hints to the
+ *     device leave such positions out;
+ *   - ffn_canvas_segment_turn flags a candidate that is not segmented but
+ *     pos_blocked or seed_blocked with cand_flags 4 (restricted): skipped, no
+ *     -1 marker (inference.py:573-574 come before the too-close test). */
+int ffn_canvas_set_restrictor(ffn_canvas* canvas, const uint8_t* mask,
+                              const uint8_t* seed_mask, const uint8_t* shift_mask,
+                              const int32_t shift_shape[3], const int32_t pre[3],
+                              const int32_t post[3], int32_t scale);
+/* dst[hi-lo] (C order, uint8): bit 0 pos_blocked, bit 1 seed_blocked; all zero
+ * without a restrictor.  The box must lie inside the canvas. */
+int ffn_canvas_read_restriction(ffn_canvas* canvas, const int32_t lo[3],
+                                const int32_t hi[3], uint8_t* dst);
+/* The segment loops' count of positions skipped for pos_blocked
+ * ("skip_restriced_pos") since the last call; reads and zeroes it. */
+int ffn_canvas_take_restricted_skips(ffn_canvas* canvas, int64_t* count);
 
 /* Box transfers between the canvas and host arrays ([hi-lo] C-order):
  * checkpoint/restore and final save (inference.py:728-821, runner.py:433-482). */
