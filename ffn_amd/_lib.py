@@ -20,8 +20,9 @@ LIB_PATH = os.environ.get('FFN_AMD_LIB') or os.path.join(CSRC, 'libffn_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'ffn_hip.h')
 HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_labels.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h')]
-SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip']
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h')]
+SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip']
 
 MAX_CANDIDATES = 16
 
@@ -260,6 +261,24 @@ SIGNATURES = {
     'ffn_seeder_read_stage': (_I, [_P, _I, _P]),
     'ffn_seeder_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                     ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_decision.h
+    'ffn_decision_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_decision_destroy': (None, [_P]),
+    'ffn_decision_expand': (_I, [_P, _P, _I, ctypes.POINTER(ctypes.c_int64),
+                                 ctypes.POINTER(ctypes.c_double),
+                                 ctypes.c_double]),
+    'ffn_decision_expand_device': (_I, [_P, _P, ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_double),
+                                        ctypes.c_double]),
+    'ffn_decision_expand_canvas': (_I, [_P, _P, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.c_double,
+                                        ctypes.POINTER(ctypes.c_int64)]),
+    'ffn_decision_read': (_I, [_P, _P, _P]),
+    'ffn_decision_contact_minima': (
+        _I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+             ctypes.c_size_t, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_decision_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None
