@@ -21,8 +21,10 @@ HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'ffn_hip.h')
 HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_labels.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h')]
-SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip']
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h')]
+SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
+           'ffn_analysis.hip']
 
 MAX_CANDIDATES = 16
 
@@ -141,6 +143,21 @@ class TurnResult(ctypes.Structure):
   """ffn_turn_result (include/ffn_hip.h)."""
   _fields_ = [('counts', CommitCounts), ('committed', ctypes.c_int32),
               ('chosen', ctypes.c_int32)]
+
+
+class PairDesc(ctypes.Structure):
+  """ffn_pair_desc (include/ffn_analysis.h)."""
+  _fields_ = [('probs', ctypes.c_void_p), ('seg', ctypes.c_void_p),
+              ('id_a', ctypes.c_uint64), ('id_b', ctypes.c_uint64),
+              ('box_zyx', ctypes.c_int32 * 3), ('off_zyx', ctypes.c_int32 * 3),
+              ('shape_zyx', ctypes.c_int32 * 3), ('reserved', ctypes.c_int32)]
+
+
+class EndpointDesc(ctypes.Structure):
+  """ffn_endpoint_desc (include/ffn_analysis.h)."""
+  _fields_ = [('probs', ctypes.c_void_p), ('seg', ctypes.c_void_p),
+              ('id', ctypes.c_uint64), ('shape_zyx', ctypes.c_int32 * 3),
+              ('has_id', ctypes.c_int32)]
 
 
 _P = ctypes.c_void_p
@@ -278,6 +295,18 @@ SIGNATURES = {
         _I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
              ctypes.c_size_t, _P, _P, _P, _P, ctypes.POINTER(ctypes.c_size_t)]),
     'ffn_decision_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_analysis.h
+    'ffn_analyzer_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_analyzer_destroy': (None, [_P]),
+    'ffn_analyzer_pair_stats': (_I, [_P, ctypes.POINTER(PairDesc),
+                                     ctypes.c_size_t, _P,
+                                     ctypes.POINTER(ctypes.c_double), _P, _P]),
+    'ffn_analyzer_endpoint_overlaps': (
+        _I, [_P, ctypes.POINTER(EndpointDesc), ctypes.c_size_t, _P,
+             ctypes.c_size_t, _P, _P, _P, _P,
+             ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_analyzer_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double)]),
 }
 

@@ -55,6 +55,41 @@ class _Repeated(list):
     return (_Repeated, (self._ftype, list(self)))
 
 
+class MapOf:
+  """Field type of a proto `map<ktype, vtype>` with message values."""
+
+  def __init__(self, ktype, vtype):
+    self.ktype, self.vtype = ktype, vtype
+
+
+class _Map(dict):
+  """Map field: `m[k]` creates the entry on first access, like protobuf's."""
+
+  __slots__ = ('_ftype', '_owner')
+
+  def __init__(self, ftype, items=()):
+    super().__init__(items)
+    self._ftype = ftype
+    self._owner = None  # (message, field name) until the first entry exists
+
+  def __missing__(self, key):
+    value = self._ftype.vtype()
+    self[self._ftype.ktype(key)] = value
+    if self._owner is not None:
+      msg, name = self._owner
+      self._owner = None
+      msg._values[name] = self
+      msg._attach()
+    return value
+
+  def __deepcopy__(self, memo):
+    return _Map(self._ftype, ((k, copy.deepcopy(v, memo))
+                              for k, v in self.items()))
+
+  def __reduce__(self):
+    return (_Map, (self._ftype, list(self.items())))
+
+
 class Message:
   """Minimal proto2-like message: typed fields, presence tracking."""
 
@@ -76,6 +111,11 @@ class Message:
     if name in values:
       return values[name]
     ftype, default, repeated = fields[name]
+    if isinstance(ftype, MapOf):
+      # present once it has an entry (an empty map prints nothing)
+      entries = _Map(ftype)
+      entries._owner = (self, name)
+      return entries
     if repeated:
       values[name] = _Repeated(ftype)
       # adding to a repeated field of a not-yet-present sub-message makes the
@@ -96,6 +136,8 @@ class Message:
     if name not in fields:
       raise AttributeError('%s has no field %r' % (type(self).__name__, name))
     ftype, _, repeated = fields[name]
+    if isinstance(ftype, MapOf):
+      raise AttributeError('map field %r is filled through its entries' % name)
     if not repeated and ftype in _SCALARS:
       if ftype is float:
         value = float(value)
@@ -139,6 +181,7 @@ class Message:
 
   def CopyFrom(self, other):  # pylint:disable=invalid-name
     object.__setattr__(self, '_values', copy.deepcopy(other._values))
+    self._attach()  # copying into an unset sub-message makes it present
 
   def __deepcopy__(self, memo):
     new = type(self)()
@@ -153,6 +196,12 @@ class Message:
     out = []
     for name, (ftype, _, repeated) in type(self).FIELDS.items():
       if name not in self._values:
+        continue
+      if isinstance(ftype, MapOf):
+        for k in sorted(self._values[name]):
+          out.append('%s%s {\n%s  key: %r\n%s  value {\n%s%s  }\n%s}\n' % (
+              pad, name, pad, k, pad,
+              self._values[name][k].to_text(indent + 2), pad, pad))
         continue
       vals = self._values[name] if repeated else [self._values[name]]
       for v in vals:
@@ -368,6 +417,77 @@ class ResegmentationRequest(Message):
       'analysis_radius': (Vector3j, None, False),
   }
 
+class _Float32Fields(Message):
+  """proto `float` fields hold f32 values: FLOAT32 names round on assignment."""
+  FLOAT32 = ()
+
+  def __setattr__(self, name, value):
+    if name in type(self).FLOAT32:
+      import numpy as np  # pylint:disable=g-import-not-at-top
+      value = float(np.float32(value))
+    super().__setattr__(name, value)
+
+
+class OverlapInfo(Message):
+  """resegmentation.proto:32-38."""
+  FIELDS = {'num_overlapping': (int, 0, False), 'num_original': (int, 0, False)}
+
+
+class EndpointResegmentationResult(Message):
+  """resegmentation.proto:22-55; `overlaps` maps an id of the original
+  segmentation to its OverlapInfo."""
+  OverlapInfo = OverlapInfo
+  FIELDS = {
+      'id': (int, 0, False),
+      'start': (Vector3j, None, False),
+      'num_voxels': (int, 0, False),
+      'overlaps': (MapOf(int, OverlapInfo), None, False),
+      'source': (OverlapInfo, None, False),
+      'segmentation_radius': (Vector3j, None, False),
+      'tag': (str, '', False),
+  }
+
+
+class SegmentResult(_Float32Fields):
+  """resegmentation.proto:72-89: metrics of one re-grown object."""
+  FIELDS = {
+      'origin': (Vector3j, None, False),
+      'num_voxels': (int, 0, False),
+      'deleted_voxels': (int, 0, False),
+      'segment_a_consistency': (float, 0.0, False),
+      'segment_b_consistency': (float, 0.0, False),
+      'max_edt': (float, 0.0, False),
+  }
+  FLOAT32 = ('segment_a_consistency', 'segment_b_consistency', 'max_edt')
+
+
+class EvalResult(_Float32Fields):
+  """resegmentation.proto:91-110."""
+  FIELDS = {
+      'radius': (Vector3j, None, False),
+      'iou': (float, 0.0, False),
+      'from_a': (SegmentResult, None, False),
+      'from_b': (SegmentResult, None, False),
+      'max_edt_a': (float, 0.0, False),
+      'max_edt_b': (float, 0.0, False),
+      'num_voxels_a': (int, 0, False),
+      'num_voxels_b': (int, 0, False),
+  }
+  FLOAT32 = ('iou', 'max_edt_a', 'max_edt_b')
+
+
+class PairResegmentationResult(Message):
+  """resegmentation.proto:57-113."""
+  SegmentResult = SegmentResult
+  EvalResult = EvalResult
+  FIELDS = {
+      'point': (Vector3j, None, False),
+      'id_a': (int, 0, False),
+      'id_b': (int, 0, False),
+      'segmentation_radius': (Vector3j, None, False),
+      'tag': (str, '', False),
+      'eval': (EvalResult, None, False),
+  }
 
 
 # ---------------------------------------------------------------------------
@@ -426,7 +546,13 @@ def _parse_fields(msg: Message, toks, i, closer):
     i += 1
     if i < len(toks) and toks[i] == ('sym', ':'):
       i += 1
-    if isinstance(ftype, type) and issubclass(ftype, Message):
+    if isinstance(ftype, MapOf):
+      if toks[i] not in (('sym', '{'), ('sym', '<')):
+        raise ValueError('expected { after %s' % name)
+      entry = _map_entry(ftype)()
+      i = _parse_fields(entry, toks, i + 1, '}' if toks[i][1] == '{' else '>')
+      getattr(msg, name)[entry.key].CopyFrom(entry.value)
+    elif isinstance(ftype, type) and issubclass(ftype, Message):
       if toks[i] not in (('sym', '{'), ('sym', '<')):
         raise ValueError('expected { after %s' % name)
       sub = ftype()
@@ -450,7 +576,9 @@ def _parse_fields(msg: Message, toks, i, closer):
       elif ftype is int:
         value = int(val) if kind == 'num' else _enum(type(msg), name, val)
       else:
-        value = float(val.rstrip('f'))
+        # 1.5f is a float literal; inf only ends in f
+        value = float(val if val.lower().endswith(('inf', 'nan'))
+                      else val.rstrip('f'))
       if repeated:
         getattr(msg, name).append(value)
       else:
@@ -458,6 +586,16 @@ def _parse_fields(msg: Message, toks, i, closer):
   if closer is not None:
     raise ValueError('unterminated message')
   return i
+
+
+def _map_entry(ftype):
+  """The `{ key: K value { ... } }` message of a map field's text format."""
+
+  class Entry(Message):
+    FIELDS = {'key': (ftype.ktype, 0, False),
+              'value': (ftype.vtype, None, False)}
+
+  return Entry
 
 
 def _enum(msg_cls, name, val):
