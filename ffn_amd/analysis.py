@@ -10,7 +10,6 @@ every call raises.
 
 from __future__ import annotations
 
-import atexit
 import collections
 import ctypes
 import threading
@@ -18,6 +17,7 @@ import threading
 import numpy as np
 
 from . import _lib
+from . import _unit
 from ._lib import check
 from .inference import storage
 
@@ -52,28 +52,14 @@ def _table(table):
   return table
 
 
-class Analyzer:
+class Analyzer(_unit.Handle):
   """One stream + grow-only device scratch for resegmentation analysis."""
 
   def __init__(self, device_id: int = 0):
-    self._lib = _lib.load()
-    self._h = ctypes.c_void_p()
-    self.device_id = int(device_id)
-    check(self._lib.ffn_analyzer_create(self.device_id, ctypes.byref(self._h)))
+    super().__init__('ffn_analyzer_create', 'ffn_analyzer_destroy', device_id)
     self.lock = threading.Lock()
     #: first row capacity of endpoint_overlaps (grown on demand)
     self.initial_cap = 1 << 14
-
-  def close(self):
-    if self._h:
-      self._lib.ffn_analyzer_destroy(self._h)
-      self._h = ctypes.c_void_p()
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
 
   def pair_stats(self, batch, table, voxel_size_zyx=(1, 1, 1)):
     """(counts uint64 [n, 10] in COUNT_NAMES order, max_edt f64 [n, 4] in
@@ -124,25 +110,24 @@ class Analyzer:
       if item.id is not None:
         d.id, d.has_id = int(item.id), 1
     num_new = np.zeros(n, np.uint64)
-    cap = max(int(self.initial_cap), 1)
+
+    def call(cap):
+      row_point = np.empty(cap, np.int32)
+      row_old = np.empty(cap, np.uint64)
+      row_counts = np.empty((cap, 2), np.uint32)
+      found = ctypes.c_size_t(0)
+      rc = self._lib.ffn_analyzer_endpoint_overlaps(
+          self._h, descs, n, table.ctypes.data, cap, row_point.ctypes.data,
+          row_old.ctypes.data, row_counts.ctypes.data, num_new.ctypes.data,
+          ctypes.byref(found))
+      return rc, found, (row_point, row_old, row_counts)
+
     with self.lock:
-      while True:
-        row_point = np.empty(cap, np.int32)
-        row_old = np.empty(cap, np.uint64)
-        row_counts = np.empty((cap, 2), np.uint32)
-        found = ctypes.c_size_t(0)
-        rc = self._lib.ffn_analyzer_endpoint_overlaps(
-            self._h, descs, n, table.ctypes.data, cap, row_point.ctypes.data,
-            row_old.ctypes.data, row_counts.ctypes.data, num_new.ctypes.data,
-            ctypes.byref(found))
-        if rc != 0 and found.value > cap:
-          cap = int(found.value)
-          continue
-        check(rc)
-        break
+      m, (row_point, row_old, row_counts) = _unit.grow_until_fits(
+          call, max(int(self.initial_cap), 1))
     del keep
     out = [(int(v), {}) for v in num_new]
-    for k in range(found.value):
+    for k in range(m):
       out[row_point[k]][1][int(row_old[k])] = (int(row_counts[k, 0]),
                                                int(row_counts[k, 1]))
     return out
@@ -156,26 +141,9 @@ class Analyzer:
     return (ms[0], voxels[0]), (ms[1], voxels[1])
 
 
-_default = {}
-_default_lock = threading.Lock()
+_default = _unit.Registry(Analyzer)
 
 
 def default_analyzer(device_id: int = 0) -> Analyzer:
   """Process-wide Analyzer of a device (created on first use)."""
-  with _default_lock:
-    a = _default.get(device_id)
-    if a is None:
-      a = Analyzer(device_id)
-      _default[device_id] = a
-    return a
-
-
-@atexit.register
-def _close_default_analyzers():
-  # release device objects while the HIP runtime is still alive
-  for a in list(_default.values()):
-    try:
-      a.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
-  _default.clear()
+  return _default.get(device_id)

@@ -34,6 +34,7 @@
 #include "../../include/ffn_hip.h"
 #include "ffn_internal.h"
 #include "ffn_table.h"
+#include "ffn_unit.h"
 
 // squared distances must round exactly as the specification's: no FMA
 #pragma clang fp contract(off)
@@ -420,68 +421,27 @@ __global__ __launch_bounds__(kThreads) void endpoint_emit_kernel(
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
+using ffn_unit::DevBuf;
+using ffn_unit::ensure;
 
 }  // namespace
 
-struct ffn_analyzer {
-  int device_id = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct ffn_analyzer : ffn_unit::Unit {
+  ffn_unit::PinnedBuf stage;  // upload staging (freed after the device buffers)
   DevBuf in, ctrl, bits, d2, small, keys, vals, rows_point, rows_old,
       rows_counts;
-  void* stage = nullptr;  // pinned upload staging
-  size_t stage_bytes = 0;
   u32 nslots = 1u << 12;  // per-point id table of the endpoint pass
   double ms[2] = {0.0, 0.0}, voxels[2] = {0.0, 0.0};
 };
 
 namespace {
 
-#define A_TRY(expr)                                                           \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess)                                                     \
-      return ffn_set_error(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,       \
-                           hipGetErrorString(_e), __FILE__, __LINE__);        \
-  } while (0)
-
-#define A_OK(expr)                 \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != FFN_OK) return _rc; \
-  } while (0)
-
-int ensure(DevBuf& buf, size_t bytes) {
-  if (buf.bytes >= bytes && buf.p) return FFN_OK;
-  if (buf.p) A_TRY(hipFree(buf.p));
-  buf.p = nullptr;
-  buf.bytes = 0;
-  A_TRY(hipMalloc(&buf.p, bytes ? bytes : 16));
-  buf.bytes = bytes ? bytes : 16;
-  return FFN_OK;
-}
-
-int ensure_stage(ffn_analyzer* a, size_t bytes) {
-  if (a->stage && a->stage_bytes >= bytes) return FFN_OK;
-  if (a->stage) A_TRY(hipHostFree(a->stage));
-  a->stage = nullptr;
-  a->stage_bytes = 0;
-  A_TRY(hipHostMalloc(&a->stage, bytes ? bytes : 16, hipHostMallocDefault));
-  a->stage_bytes = bytes ? bytes : 16;
-  return FFN_OK;
-}
-
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-int elapsed(ffn_analyzer* a, double* ms) {
-  A_TRY(hipEventRecord(a->ev1, a->stream));
-  A_TRY(hipEventSynchronize(a->ev1));
-  float t = 0.f;
-  A_TRY(hipEventElapsedTime(&t, a->ev0, a->ev1));
+// Adds the kernel time since timer_start() to *ms.
+int add_elapsed(ffn_analyzer* a, double* ms) {
+  double t = 0.0;
+  U_OK(a->timer_stop(&t));
   *ms += t;
   return FFN_OK;
 }
@@ -539,15 +499,15 @@ int run_pair_group(ffn_analyzer* a, const ffn_pair_desc* pts,
     d2_words += 4 * plans[first + i].n;
   }
   const size_t upload = in_off + in_bytes;
-  A_OK(ensure_stage(a, upload));
-  A_OK(ensure(a->in, upload));
-  A_OK(ensure(a->bits, bit_words * 8));
-  A_OK(ensure(a->d2, d2_words * 8));
+  U_OK(ensure(a->stage, upload));
+  U_OK(ensure(a->in, upload));
+  U_OK(ensure(a->bits, bit_words * 8));
+  U_OK(ensure(a->d2, d2_words * 8));
   // results: counts (10 u64), max bits (4 u64), roots (4 f64) per point
   const size_t res_bytes = count * (FFN_PAIR_COUNTS + 4 + 4) * 8;
-  A_OK(ensure(a->small, res_bytes));
+  U_OK(ensure(a->small, res_bytes));
 
-  uint8_t* stage = static_cast<uint8_t*>(a->stage);
+  uint8_t* stage = static_cast<uint8_t*>(a->stage.p);
   memcpy(stage, table, 256);
   PairDev* descs = reinterpret_cast<PairDev*>(stage + desc_off);
   int* starts = reinterpret_cast<int*>(stage + starts_off);
@@ -610,8 +570,8 @@ int run_pair_group(ffn_analyzer* a, const ffn_pair_desc* pts,
 
   hipStream_t s = a->stream;
   uint8_t* dev = static_cast<uint8_t*>(a->in.p);
-  A_TRY(hipMemcpyAsync(dev, stage, upload, hipMemcpyHostToDevice, s));
-  A_TRY(hipMemsetAsync(a->small.p, 0, res_bytes, s));
+  U_TRY(hipMemcpyAsync(dev, stage, upload, hipMemcpyHostToDevice, s));
+  U_TRY(hipMemsetAsync(a->small.p, 0, res_bytes, s));
   const PairDev* ddescs = reinterpret_cast<const PairDev*>(dev + desc_off);
   const int* dst[4];
   for (int k = 0; k < 4; ++k)
@@ -621,7 +581,7 @@ int run_pair_group(ffn_analyzer* a, const ffn_pair_desc* pts,
   double* droot = reinterpret_cast<double*>(dmax + count * 4);
   u64* bits = static_cast<u64*>(a->bits.p);
   double* d2 = static_cast<double*>(a->d2.p);
-  A_TRY(hipEventRecord(a->ev0, s));
+  U_OK(a->timer_start());
   hipLaunchKernelGGL(pair_mask_kernel, dim3((unsigned)blocks[0]), dim3(kThreads),
                      0, s, ddescs, dst[0], npts, (const uint8_t*)dev,
                      (const uint8_t*)dev, bits, dcounts);
@@ -638,13 +598,13 @@ int run_pair_group(ffn_analyzer* a, const ffn_pair_desc* pts,
                      dim3((unsigned)((count * 4 + kThreads - 1) / kThreads)),
                      dim3(kThreads), 0, s, (const u64*)dmax, droot,
                      (int)(count * 4));
-  A_TRY(hipGetLastError());
-  A_OK(elapsed(a, &a->ms[0]));
-  A_TRY(hipMemcpyAsync(counts + first * FFN_PAIR_COUNTS, dcounts,
+  U_TRY(hipGetLastError());
+  U_OK(add_elapsed(a, &a->ms[0]));
+  U_TRY(hipMemcpyAsync(counts + first * FFN_PAIR_COUNTS, dcounts,
                        count * FFN_PAIR_COUNTS * 8, hipMemcpyDeviceToHost, s));
-  A_TRY(hipMemcpyAsync(max_edt + first * 4, droot, count * 4 * 8,
+  U_TRY(hipMemcpyAsync(max_edt + first * 4, droot, count * 4 * 8,
                        hipMemcpyDeviceToHost, s));
-  A_TRY(hipStreamSynchronize(s));
+  U_TRY(hipStreamSynchronize(s));
   return FFN_OK;
 }
 
@@ -653,41 +613,10 @@ int run_pair_group(ffn_analyzer* a, const ffn_pair_desc* pts,
 extern "C" {
 
 int ffn_analyzer_create(int device_id, ffn_analyzer** out) {
-  if (!out) return ffn_set_error(FFN_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  A_TRY(hipGetDeviceCount(&ndev));
-  if (device_id < 0 || device_id >= ndev)
-    return ffn_set_error(FFN_ERR_ARG, "device %d not present (%d devices)",
-                         device_id, ndev);
-  A_TRY(hipSetDevice(device_id));
-  ffn_analyzer* a = new ffn_analyzer();
-  a->device_id = device_id;
-  hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&a->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&a->ev1);
-  if (e != hipSuccess) {
-    ffn_analyzer_destroy(a);
-    return ffn_set_error(FFN_ERR_HIP, "stream/event creation failed: %s",
-                         hipGetErrorString(e));
-  }
-  *out = a;
-  return FFN_OK;
+  return ffn_unit::unit_create(device_id, out);
 }
 
-void ffn_analyzer_destroy(ffn_analyzer* a) {
-  if (!a) return;
-  (void)hipSetDevice(a->device_id);
-  if (a->stream) (void)hipStreamSynchronize(a->stream);
-  for (DevBuf* b : {&a->in, &a->ctrl, &a->bits, &a->d2, &a->small, &a->keys,
-                    &a->vals, &a->rows_point, &a->rows_old, &a->rows_counts})
-    if (b->p) (void)hipFree(b->p);
-  if (a->stage) (void)hipHostFree(a->stage);
-  if (a->ev0) (void)hipEventDestroy(a->ev0);
-  if (a->ev1) (void)hipEventDestroy(a->ev1);
-  if (a->stream) (void)hipStreamDestroy(a->stream);
-  delete a;
-}
+void ffn_analyzer_destroy(ffn_analyzer* a) { ffn_unit::unit_destroy(a); }
 
 int ffn_analyzer_pair_stats(ffn_analyzer* a, const ffn_pair_desc* points,
                             size_t n, const uint8_t table[256],
@@ -704,8 +633,8 @@ int ffn_analyzer_pair_stats(ffn_analyzer* a, const ffn_pair_desc* points,
     if (!q.probs || !q.seg)
       return ffn_set_error(FFN_ERR_ARG, "point %zu: NULL input", i);
     size_t nv = 0, nbox = 0;
-    A_OK(check_shape(q.shape_zyx, i, &nv));
-    A_OK(check_shape(q.box_zyx, i, &nbox));
+    U_OK(check_shape(q.shape_zyx, i, &nv));
+    U_OK(check_shape(q.box_zyx, i, &nbox));
     for (int k = 0; k < 3; ++k)
       if (q.off_zyx[k] < 0 ||
           (long long)q.off_zyx[k] + q.shape_zyx[k] > q.box_zyx[k])
@@ -713,7 +642,7 @@ int ffn_analyzer_pair_stats(ffn_analyzer* a, const ffn_pair_desc* points,
                              "point %zu: crop leaves the box on axis %d", i, k);
     plans[i] = plan_pair(q, nv);
   }
-  A_TRY(hipSetDevice(a->device_id));
+  U_TRY(hipSetDevice(a->device_id));
   a->ms[0] = 0.0;
   a->voxels[0] = 0.0;
   size_t first = 0;
@@ -727,7 +656,7 @@ int ffn_analyzer_pair_stats(ffn_analyzer* a, const ffn_pair_desc* points,
       a->voxels[0] += (double)pl.n;
       ++count;
     }
-    A_OK(run_pair_group(a, points, plans, first, count, table, voxel_size_zyx,
+    U_OK(run_pair_group(a, points, plans, first, count, table, voxel_size_zyx,
                         counts, max_edt));
     first += count;
   }
@@ -748,21 +677,21 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
   for (size_t i = 0; i < n; ++i) {
     if (!points[i].probs || !points[i].seg)
       return ffn_set_error(FFN_ERR_ARG, "point %zu: NULL input", i);
-    A_OK(check_shape(points[i].shape_zyx, i, &nv[i]));
+    U_OK(check_shape(points[i].shape_zyx, i, &nv[i]));
   }
-  A_TRY(hipSetDevice(a->device_id));
+  U_TRY(hipSetDevice(a->device_id));
   a->ms[1] = 0.0;
   a->voxels[1] = 0.0;
   hipStream_t s = a->stream;
-  A_OK(ensure(a->rows_point, cap * 4));
-  A_OK(ensure(a->rows_old, cap * 8));
-  A_OK(ensure(a->rows_counts, cap * 8));
+  U_OK(ensure(a->rows_point, cap * 4));
+  U_OK(ensure(a->rows_old, cap * 8));
+  U_OK(ensure(a->rows_counts, cap * 8));
   // flags (overflow, bad id) and the row counter live apart from the
   // per-group results so that the counter runs on across groups
-  A_OK(ensure(a->ctrl, 64));
+  U_OK(ensure(a->ctrl, 64));
   int* flags = static_cast<int*>(a->ctrl.p);
   u64* n_out = reinterpret_cast<u64*>(a->ctrl.p) + 1;
-  A_TRY(hipMemsetAsync(a->ctrl.p, 0, 64, s));
+  U_TRY(hipMemsetAsync(a->ctrl.p, 0, 64, s));
   size_t first = 0;
   while (first < n) {
     size_t count = 0, bytes = 0;
@@ -778,10 +707,10 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
     const size_t starts_off = align16(desc_off + count * sizeof(EndDev));
     const size_t in_off = align16(starts_off + (count + 1) * sizeof(int));
     const size_t upload = in_off + bytes;
-    A_OK(ensure_stage(a, upload));
-    A_OK(ensure(a->in, upload));
-    A_OK(ensure(a->small, count * 8));
-    uint8_t* stage = static_cast<uint8_t*>(a->stage);
+    U_OK(ensure(a->stage, upload));
+    U_OK(ensure(a->in, upload));
+    U_OK(ensure(a->small, count * 8));
+    uint8_t* stage = static_cast<uint8_t*>(a->stage.p);
     memcpy(stage, table, 256);
     EndDev* descs = reinterpret_cast<EndDev*>(stage + desc_off);
     int* starts = reinterpret_cast<int*>(stage + starts_off);
@@ -804,16 +733,16 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
     }
     starts[count] = (int)blocks;
     uint8_t* dev = static_cast<uint8_t*>(a->in.p);
-    A_TRY(hipMemcpyAsync(dev, stage, upload, hipMemcpyHostToDevice, s));
+    U_TRY(hipMemcpyAsync(dev, stage, upload, hipMemcpyHostToDevice, s));
     for (;;) {
       const size_t slots = (size_t)a->nslots * count;
-      A_OK(ensure(a->keys, slots * 8));
-      A_OK(ensure(a->vals, slots * 8));
-      A_TRY(hipMemsetAsync(a->keys.p, 0xff, slots * 8, s));
-      A_TRY(hipMemsetAsync(a->vals.p, 0, slots * 8, s));
-      A_TRY(hipMemsetAsync(a->small.p, 0, count * 8, s));
-      A_TRY(hipMemsetAsync(flags, 0, 8, s));
-      A_TRY(hipEventRecord(a->ev0, s));
+      U_OK(ensure(a->keys, slots * 8));
+      U_OK(ensure(a->vals, slots * 8));
+      U_TRY(hipMemsetAsync(a->keys.p, 0xff, slots * 8, s));
+      U_TRY(hipMemsetAsync(a->vals.p, 0, slots * 8, s));
+      U_TRY(hipMemsetAsync(a->small.p, 0, count * 8, s));
+      U_TRY(hipMemsetAsync(flags, 0, 8, s));
+      U_OK(a->timer_start());
       hipLaunchKernelGGL(
           endpoint_count_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s,
           reinterpret_cast<const EndDev*>(dev + desc_off),
@@ -821,10 +750,10 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
           (const uint8_t*)dev, (const uint8_t*)dev,
           static_cast<u64*>(a->keys.p), static_cast<u32*>(a->vals.p),
           a->nslots - 1, flags, static_cast<u64*>(a->small.p));
-      A_TRY(hipGetLastError());
-      A_OK(elapsed(a, &a->ms[1]));
+      U_TRY(hipGetLastError());
+      U_OK(add_elapsed(a, &a->ms[1]));
       int host_flags[2] = {0, 0};
-      A_TRY(hipMemcpy(host_flags, flags, 8, hipMemcpyDeviceToHost));
+      U_TRY(hipMemcpy(host_flags, flags, 8, hipMemcpyDeviceToHost));
       if (host_flags[1])
         return ffn_set_error(FFN_ERR_ARG, "segment id 2^64 - 1 is not supported");
       if (!host_flags[0]) break;
@@ -834,7 +763,7 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
       a->nslots <<= 2;
     }
     const long long total = (long long)a->nslots * (long long)count;
-    A_TRY(hipEventRecord(a->ev0, s));
+    U_OK(a->timer_start());
     hipLaunchKernelGGL(endpoint_emit_kernel,
                        dim3((unsigned)((total + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, s,
@@ -845,23 +774,23 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
                        static_cast<int*>(a->rows_point.p),
                        static_cast<u64*>(a->rows_old.p),
                        static_cast<u32*>(a->rows_counts.p));
-    A_TRY(hipGetLastError());
-    A_OK(elapsed(a, &a->ms[1]));
-    A_TRY(hipMemcpy(num_new + first, a->small.p, count * 8,
+    U_TRY(hipGetLastError());
+    U_OK(add_elapsed(a, &a->ms[1]));
+    U_TRY(hipMemcpy(num_new + first, a->small.p, count * 8,
                     hipMemcpyDeviceToHost));
     first += count;
   }
   u64 found = 0;
-  A_TRY(hipMemcpy(&found, n_out, 8, hipMemcpyDeviceToHost));
+  U_TRY(hipMemcpy(&found, n_out, 8, hipMemcpyDeviceToHost));
   *n_rows = (size_t)found;
   if (found > cap)
     return ffn_set_error(FFN_ERR_ARG, "%llu rows exceed cap %zu", found, cap);
   if (found) {
-    A_TRY(hipMemcpy(row_point, a->rows_point.p, (size_t)found * 4,
+    U_TRY(hipMemcpy(row_point, a->rows_point.p, (size_t)found * 4,
                     hipMemcpyDeviceToHost));
-    A_TRY(hipMemcpy(row_old, a->rows_old.p, (size_t)found * 8,
+    U_TRY(hipMemcpy(row_old, a->rows_old.p, (size_t)found * 8,
                     hipMemcpyDeviceToHost));
-    A_TRY(hipMemcpy(row_counts, a->rows_counts.p, (size_t)found * 8,
+    U_TRY(hipMemcpy(row_counts, a->rows_counts.p, (size_t)found * 8,
                     hipMemcpyDeviceToHost));
   }
   return FFN_OK;

@@ -24,6 +24,7 @@
 #include "../../include/ffn_hip.h"
 #include "ffn_internal.h"
 #include "ffn_table.h"
+#include "ffn_unit.h"
 
 // d2 sums must round exactly as the specification's: no FMA contraction.
 #pragma clang fp contract(off)
@@ -361,17 +362,12 @@ __global__ __launch_bounds__(kThreads) void contact_emit_kernel(
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
+using ffn_unit::DevBuf;
+using ffn_unit::ensure;
 
 }  // namespace
 
-struct ffn_decision {
-  int device_id = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct ffn_decision : ffn_unit::Unit {
   DevBuf in, d2, id, keys, vals, out_key, out_dist, out_off, small;
   long long shape[3] = {0, 0, 0};
   bool valid = false;  // an expansion is resident
@@ -380,39 +376,6 @@ struct ffn_decision {
 };
 
 namespace {
-
-#define D_TRY(expr)                                                           \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess)                                                     \
-      return ffn_set_error(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,       \
-                           hipGetErrorString(_e), __FILE__, __LINE__);        \
-  } while (0)
-
-#define D_OK(expr)                 \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != FFN_OK) return _rc; \
-  } while (0)
-
-int ensure(DevBuf& buf, size_t bytes) {
-  if (buf.bytes >= bytes && buf.p) return FFN_OK;
-  if (buf.p) D_TRY(hipFree(buf.p));
-  buf.p = nullptr;
-  buf.bytes = 0;
-  D_TRY(hipMalloc(&buf.p, bytes ? bytes : 16));
-  buf.bytes = bytes ? bytes : 16;
-  return FFN_OK;
-}
-
-int elapsed(ffn_decision* h, double* ms) {
-  D_TRY(hipEventRecord(h->ev1, h->stream));
-  D_TRY(hipEventSynchronize(h->ev1));
-  float t = 0.f;
-  D_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
-  *ms = t;
-  return FFN_OK;
-}
 
 int check_geometry(const int64_t shape[3], const double voxel[3]) {
   if (!shape || !voxel) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
@@ -444,15 +407,15 @@ int expand_impl(ffn_decision* h, const T* seg, const int64_t shape[3],
   const long long nz = shape[0], ny = shape[1], nx = shape[2];
   const size_t n = (size_t)nz * ny * nx;
   h->valid = false;
-  D_OK(ensure(h->d2, n * 8));
-  D_OK(ensure(h->id, n * 4));
-  D_OK(ensure(h->small, 64));
-  D_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+  U_OK(ensure(h->d2, n * 8));
+  U_OK(ensure(h->id, n * 4));
+  U_OK(ensure(h->small, 64));
+  U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
   double* d2 = static_cast<double*>(h->d2.p);
   u32* id = static_cast<u32*>(h->id.p);
   int* bad = static_cast<int*>(h->small.p);
   const double maxd = max_distance >= 0.0 ? max_distance : -1.0;  // NaN -> -1
-  D_TRY(hipEventRecord(h->ev0, h->stream));
+  U_OK(h->timer_start());
   {
     const long long rows = nz * ny;
     int waves = kThreads / 64;
@@ -479,11 +442,11 @@ int expand_impl(ffn_decision* h, const T* seg, const int64_t shape[3],
                        h->stream, d2, id, (int)nz, cols, cols, 0LL,
                        voxel_xyz[2], tx, 1, maxd);
   }
-  D_TRY(hipGetLastError());
-  D_OK(elapsed(h, &h->ms[0]));
+  U_TRY(hipGetLastError());
+  U_OK(h->timer_stop(&h->ms[0]));
   h->bytes[0] = (double)n * (sizeof(T) + 5.0 * kLineBytesPerVoxel);
   int flag = 0;
-  D_TRY(hipMemcpy(&flag, bad, sizeof(int), hipMemcpyDeviceToHost));
+  U_TRY(hipMemcpy(&flag, bad, sizeof(int), hipMemcpyDeviceToHost));
   if (flag)
     return ffn_set_error(FFN_ERR_ARG,
                          "label id >= 2^32 - 1: remap ids before expanding");
@@ -497,40 +460,10 @@ int expand_impl(ffn_decision* h, const T* seg, const int64_t shape[3],
 extern "C" {
 
 int ffn_decision_create(int device_id, ffn_decision** out) {
-  if (!out) return ffn_set_error(FFN_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  D_TRY(hipGetDeviceCount(&ndev));
-  if (device_id < 0 || device_id >= ndev)
-    return ffn_set_error(FFN_ERR_ARG, "device %d not present (%d devices)",
-                         device_id, ndev);
-  D_TRY(hipSetDevice(device_id));
-  ffn_decision* h = new ffn_decision();
-  h->device_id = device_id;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-  if (e != hipSuccess) {
-    ffn_decision_destroy(h);
-    return ffn_set_error(FFN_ERR_HIP, "stream/event creation failed: %s",
-                         hipGetErrorString(e));
-  }
-  *out = h;
-  return FFN_OK;
+  return ffn_unit::unit_create(device_id, out);
 }
 
-void ffn_decision_destroy(ffn_decision* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device_id);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf* b : {&h->in, &h->d2, &h->id, &h->keys, &h->vals, &h->out_key,
-                    &h->out_dist, &h->out_off, &h->small})
-    if (b->p) (void)hipFree(b->p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void ffn_decision_destroy(ffn_decision* h) { ffn_unit::unit_destroy(h); }
 
 int ffn_decision_expand(ffn_decision* h, const void* seg, int elem_bytes,
                         const int64_t shape_zyx[3],
@@ -538,12 +471,12 @@ int ffn_decision_expand(ffn_decision* h, const void* seg, int elem_bytes,
   if (!h || !seg) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   if (elem_bytes != 4 && elem_bytes != 8)
     return ffn_set_error(FFN_ERR_ARG, "elem_bytes must be 4 or 8");
-  D_OK(check_geometry(shape_zyx, voxel_size_xyz));
-  D_TRY(hipSetDevice(h->device_id));
+  U_OK(check_geometry(shape_zyx, voxel_size_xyz));
+  U_TRY(hipSetDevice(h->device_id));
   const size_t n = (size_t)shape_zyx[0] * shape_zyx[1] * shape_zyx[2];
   h->valid = false;
-  D_OK(ensure(h->in, n * elem_bytes));
-  D_TRY(hipMemcpyAsync(h->in.p, seg, n * elem_bytes, hipMemcpyHostToDevice,
+  U_OK(ensure(h->in, n * elem_bytes));
+  U_TRY(hipMemcpyAsync(h->in.p, seg, n * elem_bytes, hipMemcpyHostToDevice,
                        h->stream));
   if (elem_bytes == 4)
     return expand_impl<uint32_t>(h, static_cast<const uint32_t*>(h->in.p),
@@ -557,8 +490,8 @@ int ffn_decision_expand_device(ffn_decision* h, const int32_t* seg_dev,
                                const double voxel_size_xyz[3],
                                double max_distance) {
   if (!h || !seg_dev) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  D_OK(check_geometry(shape_zyx, voxel_size_xyz));
-  D_TRY(hipSetDevice(h->device_id));
+  U_OK(check_geometry(shape_zyx, voxel_size_xyz));
+  U_TRY(hipSetDevice(h->device_id));
   return expand_impl<int32_t>(h, seg_dev, shape_zyx, voxel_size_xyz,
                               max_distance);
 }
@@ -568,13 +501,13 @@ int ffn_decision_expand_canvas(ffn_decision* h, ffn_canvas* canvas,
                                double max_distance, int64_t shape_zyx_out[3]) {
   if (!h || !canvas) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   FfnCanvasView v;
-  D_OK(ffn_canvas_view(canvas, &v));
+  U_OK(ffn_canvas_view(canvas, &v));
   if (v.device_id != h->device_id)
     return ffn_set_error(FFN_ERR_ARG, "canvas lives on device %d, handle on %d",
                          v.device_id, h->device_id);
-  D_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   // the canvas' own stream may still be committing the last segment
-  D_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
+  U_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
   const int64_t shape[3] = {v.shape_zyx[0], v.shape_zyx[1], v.shape_zyx[2]};
   if (shape_zyx_out)
     for (int k = 0; k < 3; ++k) shape_zyx_out[k] = shape[k];
@@ -587,11 +520,11 @@ int ffn_decision_read(ffn_decision* h, uint32_t* expanded, double* edt) {
   if (!h->valid)
     return ffn_set_error(FFN_ERR_STATE,
                          "no expansion resident: call ffn_decision_expand");
-  D_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   const size_t n = (size_t)h->shape[0] * h->shape[1] * h->shape[2];
   if (expanded)
-    D_TRY(hipMemcpy(expanded, h->id.p, n * 4, hipMemcpyDeviceToHost));
-  if (edt) D_TRY(hipMemcpy(edt, h->d2.p, n * 8, hipMemcpyDeviceToHost));
+    U_TRY(hipMemcpy(expanded, h->id.p, n * 4, hipMemcpyDeviceToHost));
+  if (edt) U_TRY(hipMemcpy(edt, h->d2.p, n * 8, hipMemcpyDeviceToHost));
   return FFN_OK;
 }
 
@@ -626,40 +559,40 @@ int ffn_decision_contact_minima(ffn_decision* h, const int64_t lo_zyx[3],
   h->ms[1] = 0.0;
   h->bytes[1] = 0.0;
   if (g.n == 0) return FFN_OK;
-  D_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   const u32* id = static_cast<const u32*>(h->id.p);
   const double* edt = static_cast<const double*>(h->d2.p);
-  D_OK(ensure(h->small, 64));
+  U_OK(ensure(h->small, 64));
   int* overflow = static_cast<int*>(h->small.p);
   u64* n_out = reinterpret_cast<u64*>(h->small.p) + 1;
   u32 nslots = std::max<u32>(h->nslots, 1u << 18);
   double ms = 0.0;
   for (;;) {
-    D_OK(ensure(h->keys, (size_t)nslots * 8));
-    D_OK(ensure(h->vals, (size_t)nslots * 8));
-    D_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
-    D_TRY(hipMemsetAsync(h->vals.p, 0xff, (size_t)nslots * 8, h->stream));
-    D_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
-    D_TRY(hipEventRecord(h->ev0, h->stream));
+    U_OK(ensure(h->keys, (size_t)nslots * 8));
+    U_OK(ensure(h->vals, (size_t)nslots * 8));
+    U_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
+    U_TRY(hipMemsetAsync(h->vals.p, 0xff, (size_t)nslots * 8, h->stream));
+    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+    U_OK(h->timer_start());
     const int blocks = (int)std::min<long long>(
         2048, std::max<long long>(1, (g.n + 16 * kThreads - 1) / (16 * kThreads)));
     hipLaunchKernelGGL(contact_min_kernel, dim3(blocks), dim3(kThreads), 0,
                        h->stream, id, edt, g, static_cast<u64*>(h->keys.p),
                        static_cast<u64*>(h->vals.p), nslots - 1, overflow);
-    D_TRY(hipGetLastError());
-    D_OK(elapsed(h, &ms));
+    U_TRY(hipGetLastError());
+    U_OK(h->timer_stop(&ms));
     int ov = 0;
-    D_TRY(hipMemcpy(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost));
+    U_TRY(hipMemcpy(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost));
     if (!ov) break;
     if (nslots >= (1u << 28))
       return ffn_set_error(FFN_ERR_ARG, "pair table overflow at 2^28 slots");
     nslots <<= 2;
   }
   h->nslots = nslots;
-  D_OK(ensure(h->out_key, cap * 8));
-  D_OK(ensure(h->out_dist, cap * 8));
-  D_OK(ensure(h->out_off, cap * 16));
-  D_TRY(hipEventRecord(h->ev0, h->stream));
+  U_OK(ensure(h->out_key, cap * 8));
+  U_OK(ensure(h->out_dist, cap * 8));
+  U_OK(ensure(h->out_off, cap * 16));
+  U_OK(h->timer_start());
   {
     const int blocks = (int)std::min<long long>(
         4096, std::max<long long>(1, (g.n + kThreads - 1) / kThreads));
@@ -670,27 +603,27 @@ int ffn_decision_contact_minima(ffn_decision* h, const int64_t lo_zyx[3],
                        n_out, static_cast<u64*>(h->out_key.p),
                        static_cast<double*>(h->out_dist.p),
                        static_cast<int*>(h->out_off.p));
-    D_TRY(hipGetLastError());
+    U_TRY(hipGetLastError());
   }
   double ms2 = 0.0;
-  D_OK(elapsed(h, &ms2));
+  U_OK(h->timer_stop(&ms2));
   h->ms[1] = ms + ms2;
   // both sweeps read id + distance of every voxel of the crop once (the
   // neighbour reads hit the caches)
   h->bytes[1] = 2.0 * (double)g.n * kLineBytesPerVoxel;
   u64 found = 0;
-  D_TRY(hipMemcpy(&found, n_out, sizeof(u64), hipMemcpyDeviceToHost));
+  U_TRY(hipMemcpy(&found, n_out, sizeof(u64), hipMemcpyDeviceToHost));
   *n = (size_t)found;
   if (found > cap)
     return ffn_set_error(FFN_ERR_ARG, "%llu candidates exceed cap %zu", found,
                          cap);
   if (found == 0) return FFN_OK;
   std::vector<u64> keys(found);
-  D_TRY(hipMemcpy(keys.data(), h->out_key.p, (size_t)found * 8,
+  U_TRY(hipMemcpy(keys.data(), h->out_key.p, (size_t)found * 8,
                   hipMemcpyDeviceToHost));
-  D_TRY(hipMemcpy(dist, h->out_dist.p, (size_t)found * 8,
+  U_TRY(hipMemcpy(dist, h->out_dist.p, (size_t)found * 8,
                   hipMemcpyDeviceToHost));
-  D_TRY(hipMemcpy(off_zyx, h->out_off.p, (size_t)found * 16,
+  U_TRY(hipMemcpy(off_zyx, h->out_off.p, (size_t)found * 16,
                   hipMemcpyDeviceToHost));
   for (u64 k = 0; k < found; ++k) {
     pair_a[k] = keys[k] & 0xffffffffull;

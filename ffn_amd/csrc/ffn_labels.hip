@@ -15,6 +15,7 @@
 #include "../../include/ffn_labels.h"
 #include "ffn_internal.h"
 #include "ffn_table.h"
+#include "ffn_unit.h"
 
 namespace {
 
@@ -430,17 +431,12 @@ __global__ __launch_bounds__(kThreads) void margin_gather_kernel(
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
+using ffn_unit::DevBuf;
+using ffn_unit::ensure;
 
 }  // namespace
 
-struct ffn_labels {
-  int device_id = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+struct ffn_labels : ffn_unit::Unit {
   DevBuf a, b, out, keys, counts, slot_label, aux0, aux1, aux2, small;
   u32 nslots = 0;  // size of the resident hash table (pair_counts)
   size_t n = 0;    // voxels of the resident volumes
@@ -452,45 +448,12 @@ struct ffn_labels {
 
 namespace {
 
-#define L_TRY(expr)                                                           \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess)                                                     \
-      return ffn_set_error(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,       \
-                           hipGetErrorString(_e), __FILE__, __LINE__);        \
-  } while (0)
-
-int ensure(DevBuf& buf, size_t bytes) {
-  if (buf.bytes >= bytes && buf.p) return FFN_OK;
-  if (buf.p) L_TRY(hipFree(buf.p));
-  buf.p = nullptr;
-  buf.bytes = 0;
-  L_TRY(hipMalloc(&buf.p, bytes ? bytes : 16));
-  buf.bytes = bytes ? bytes : 16;
-  return FFN_OK;
-}
-
-#define L_OK(expr)                \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != FFN_OK) return _rc; \
-  } while (0)
-
 int grid_for(size_t n, int per_block) {
   return (int)std::min<size_t>((n + per_block - 1) / per_block, 1u << 30);
 }
 
-int start_timer(ffn_labels* h) {
-  L_TRY(hipEventRecord(h->ev0, h->stream));
-  return FFN_OK;
-}
-
 int stop_timer(ffn_labels* h, double bytes) {
-  L_TRY(hipEventRecord(h->ev1, h->stream));
-  L_TRY(hipEventSynchronize(h->ev1));
-  float ms = 0.f;
-  L_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms;
+  U_OK(h->timer_stop(&h->last_ms));
   h->last_bytes = bytes;
   return FFN_OK;
 }
@@ -502,12 +465,12 @@ u32 table_size_for(size_t expected) {
 }
 
 int alloc_table(ffn_labels* h, u32 nslots, bool with_counts) {
-  L_OK(ensure(h->keys, (size_t)nslots * 8));
-  L_OK(ensure(h->slot_label, (size_t)nslots * 8));
-  if (with_counts) L_OK(ensure(h->counts, (size_t)nslots * 8));
-  L_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
+  U_OK(ensure(h->keys, (size_t)nslots * 8));
+  U_OK(ensure(h->slot_label, (size_t)nslots * 8));
+  if (with_counts) U_OK(ensure(h->counts, (size_t)nslots * 8));
+  U_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
   if (with_counts)
-    L_TRY(hipMemsetAsync(h->counts.p, 0, (size_t)nslots * 8, h->stream));
+    U_TRY(hipMemsetAsync(h->counts.p, 0, (size_t)nslots * 8, h->stream));
   return FFN_OK;
 }
 
@@ -517,25 +480,25 @@ int pair_counts_impl(ffn_labels* h, size_t n, size_t cap, uint64_t* pair_a,
                      uint32_t* pair_slot, size_t* n_pairs) {
   const T* a = static_cast<const T*>(h->a.p);
   const T* b = h->have_b ? static_cast<const T*>(h->b.p) : nullptr;
-  L_OK(ensure(h->small, 64));
+  U_OK(ensure(h->small, 64));
   int* overflow = static_cast<int*>(h->small.p);
   u32* n_out = reinterpret_cast<u32*>(h->small.p) + 1;
   u32 nslots = std::max<u32>(h->nslots, 1u << 20);
   for (;;) {
-    L_OK(alloc_table(h, nslots, true));
-    L_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
-    L_OK(start_timer(h));
+    U_OK(alloc_table(h, nslots, true));
+    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+    U_OK(h->timer_start());
     const int blocks = (int)std::min<size_t>(
         2048, std::max<size_t>(1, (n + 16 * kThreads - 1) / (16 * kThreads)));
     hipLaunchKernelGGL((pair_count_kernel<T>), dim3(blocks), dim3(kThreads), 0,
                        h->stream, a, b, n, static_cast<u64*>(h->keys.p),
                        static_cast<u64*>(h->counts.p), nslots - 1, overflow);
-    L_TRY(hipGetLastError());
-    L_OK(stop_timer(h, (double)n * sizeof(T) * (b ? 2 : 1)));
+    U_TRY(hipGetLastError());
+    U_OK(stop_timer(h, (double)n * sizeof(T) * (b ? 2 : 1)));
     int ov = 0;
-    L_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
+    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
                          h->stream));
-    L_TRY(hipStreamSynchronize(h->stream));
+    U_TRY(hipStreamSynchronize(h->stream));
     if (!ov) break;
     if (ov == 2)
       return ffn_set_error(FFN_ERR_ARG,
@@ -547,30 +510,30 @@ int pair_counts_impl(ffn_labels* h, size_t n, size_t cap, uint64_t* pair_a,
   h->nslots = nslots;
   // compact the occupied slots into dense arrays (order unspecified)
   const size_t want = std::min<size_t>(cap, nslots);
-  L_OK(ensure(h->aux0, want * 8));
-  L_OK(ensure(h->aux1, want * 8));
-  L_OK(ensure(h->aux2, want * 4));
+  U_OK(ensure(h->aux0, want * 8));
+  U_OK(ensure(h->aux1, want * 8));
+  U_OK(ensure(h->aux2, want * 4));
   hipLaunchKernelGGL(table_compact_kernel, dim3((nslots + 255) / 256),
                      dim3(256), 0, h->stream,
                      static_cast<const u64*>(h->keys.p),
                      static_cast<const u64*>(h->counts.p), nslots,
                      static_cast<u64*>(h->aux0.p), static_cast<u64*>(h->aux1.p),
                      static_cast<u32*>(h->aux2.p), (u32)want, n_out);
-  L_TRY(hipGetLastError());
+  U_TRY(hipGetLastError());
   u32 found = 0;
-  L_TRY(hipMemcpyAsync(&found, n_out, sizeof(u32), hipMemcpyDeviceToHost,
+  U_TRY(hipMemcpyAsync(&found, n_out, sizeof(u32), hipMemcpyDeviceToHost,
                        h->stream));
-  L_TRY(hipStreamSynchronize(h->stream));
+  U_TRY(hipStreamSynchronize(h->stream));
   *n_pairs = found;
   if (found > cap)
     return ffn_set_error(FFN_ERR_ARG, "%u unique pairs exceed cap %zu", found,
                          cap);
   std::vector<u64> keys(found);
-  L_TRY(hipMemcpy(keys.data(), h->aux0.p, (size_t)found * 8,
+  U_TRY(hipMemcpy(keys.data(), h->aux0.p, (size_t)found * 8,
                   hipMemcpyDeviceToHost));
-  L_TRY(hipMemcpy(pair_count, h->aux1.p, (size_t)found * 8,
+  U_TRY(hipMemcpy(pair_count, h->aux1.p, (size_t)found * 8,
                   hipMemcpyDeviceToHost));
-  L_TRY(hipMemcpy(pair_slot, h->aux2.p, (size_t)found * 4,
+  U_TRY(hipMemcpy(pair_slot, h->aux2.p, (size_t)found * 4,
                   hipMemcpyDeviceToHost));
   for (u32 k = 0; k < found; ++k) {
     pair_a[k] = h->have_b ? (keys[k] & 0xffffffffull) : keys[k];
@@ -589,7 +552,7 @@ int apply_impl(ffn_labels* h, const T* a, const T* b, size_t n, int missing,
                      h->stream, a, b, n, static_cast<const u64*>(h->keys.p),
                      static_cast<const u64*>(h->slot_label.p), h->nslots - 1,
                      missing, out);
-  L_TRY(hipGetLastError());
+  U_TRY(hipGetLastError());
   return FFN_OK;
 }
 
@@ -607,9 +570,9 @@ int cc_impl(ffn_labels* h, u32 n, const CcGeom& g, size_t cap,
   u64* first_index = want_first ? static_cast<u64*>(h->keys.p) : nullptr;
   u64* sizes = want_sizes ? static_cast<u64*>(h->counts.p) : nullptr;
   const int blocks = (int)((n + kThreads - 1) / kThreads);
-  L_TRY(hipMemsetAsync(h->small.p, 0xff, 4, h->stream));
-  if (sizes) L_TRY(hipMemsetAsync(sizes, 0, cap * 8, h->stream));
-  L_OK(start_timer(h));
+  U_TRY(hipMemsetAsync(h->small.p, 0xff, 4, h->stream));
+  if (sizes) U_TRY(hipMemsetAsync(sizes, 0, cap * 8, h->stream));
+  U_OK(h->timer_start());
   hipLaunchKernelGGL((cc_init_kernel<T>), dim3(blocks), dim3(kThreads), 0,
                      h->stream, in, n, g.nx, parent, first_zero);
   hipLaunchKernelGGL((cc_merge_kernel<T>), dim3(blocks), dim3(kThreads), 0,
@@ -624,12 +587,12 @@ int cc_impl(ffn_labels* h, u32 n, const CcGeom& g, size_t cap,
                      h->stream, parent, n, tiles, newid, first_index, (u32)cap);
   hipLaunchKernelGGL((cc_output_kernel<T>), dim3(blocks), dim3(kThreads), 0,
                      h->stream, parent, newid, n, out, sizes, (u32)cap);
-  L_TRY(hipGetLastError());
+  U_TRY(hipGetLastError());
   // in read by init + merge (neighbour reads hit L2), parent/newid traffic,
   // out written: 2 * sizeof(T) + 5 * 4 bytes per voxel is the streaming floor.
-  L_OK(stop_timer(h, (double)n * (2 * sizeof(T) + 20)));
+  U_OK(stop_timer(h, (double)n * (2 * sizeof(T) + 20)));
   u32 host[2] = {0, 0};
-  L_TRY(hipMemcpy(host, h->small.p, 8, hipMemcpyDeviceToHost));
+  U_TRY(hipMemcpy(host, h->small.p, 8, hipMemcpyDeviceToHost));
   *n_components = host[1];
   h->last_bytes = (double)n * (2 * sizeof(T) + 20);
   // host[0] = first zero index (0xffffffff if none); returned by the caller
@@ -641,40 +604,10 @@ int cc_impl(ffn_labels* h, u32 n, const CcGeom& g, size_t cap,
 extern "C" {
 
 int ffn_labels_create(int device_id, ffn_labels** out) {
-  if (!out) return ffn_set_error(FFN_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  L_TRY(hipGetDeviceCount(&ndev));
-  if (device_id < 0 || device_id >= ndev)
-    return ffn_set_error(FFN_ERR_ARG, "device %d not present (%d devices)",
-                         device_id, ndev);
-  L_TRY(hipSetDevice(device_id));
-  ffn_labels* h = new ffn_labels();
-  h->device_id = device_id;
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-  if (e != hipSuccess) {
-    ffn_labels_destroy(h);
-    return ffn_set_error(FFN_ERR_HIP, "stream/event creation failed: %s",
-                         hipGetErrorString(e));
-  }
-  *out = h;
-  return FFN_OK;
+  return ffn_unit::unit_create(device_id, out);
 }
 
-void ffn_labels_destroy(ffn_labels* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device_id);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf* b : {&h->a, &h->b, &h->out, &h->keys, &h->counts,
-                    &h->slot_label, &h->aux0, &h->aux1, &h->aux2, &h->small})
-    if (b->p) (void)hipFree(b->p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void ffn_labels_destroy(ffn_labels* h) { ffn_unit::unit_destroy(h); }
 
 int ffn_labels_pair_counts(ffn_labels* h, const void* a, const void* b,
                            int elem_bytes, size_t n, size_t cap,
@@ -685,7 +618,7 @@ int ffn_labels_pair_counts(ffn_labels* h, const void* a, const void* b,
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   if (elem_bytes != 4 && elem_bytes != 8)
     return ffn_set_error(FFN_ERR_ARG, "elem_bytes must be 4 or 8");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   *n_pairs = 0;
   h->n = n;
@@ -693,19 +626,19 @@ int ffn_labels_pair_counts(ffn_labels* h, const void* a, const void* b,
   h->have_b = b != nullptr;
   if (n == 0) {
     h->nslots = std::max<u32>(h->nslots, 1u << 20);
-    L_OK(alloc_table(h, h->nslots, true));
-    L_TRY(hipStreamSynchronize(h->stream));
+    U_OK(alloc_table(h, h->nslots, true));
+    U_TRY(hipStreamSynchronize(h->stream));
     h->pairs_valid = true;
     h->last_ms = 0.0;
     h->last_bytes = 0.0;
     return FFN_OK;
   }
-  L_OK(ensure(h->a, n * elem_bytes));
-  L_TRY(hipMemcpyAsync(h->a.p, a, n * elem_bytes, hipMemcpyHostToDevice,
+  U_OK(ensure(h->a, n * elem_bytes));
+  U_TRY(hipMemcpyAsync(h->a.p, a, n * elem_bytes, hipMemcpyHostToDevice,
                        h->stream));
   if (b) {
-    L_OK(ensure(h->b, n * elem_bytes));
-    L_TRY(hipMemcpyAsync(h->b.p, b, n * elem_bytes, hipMemcpyHostToDevice,
+    U_OK(ensure(h->b, n * elem_bytes));
+    U_TRY(hipMemcpyAsync(h->b.p, b, n * elem_bytes, hipMemcpyHostToDevice,
                          h->stream));
   }
   if (elem_bytes == 4)
@@ -723,19 +656,19 @@ int ffn_labels_apply_pair_labels(ffn_labels* h, size_t n_pairs,
   if (!h->pairs_valid)
     return ffn_set_error(FFN_ERR_STATE,
                          "no pair table resident: call ffn_labels_pair_counts");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   if (h->n == 0) return FFN_OK;
   for (size_t k = 0; k < n_pairs; ++k)
     if (pair_slot[k] >= h->nslots)
       return ffn_set_error(FFN_ERR_ARG, "pair_slot[%zu] out of range", k);
-  L_OK(ensure(h->aux2, n_pairs * 4));
-  L_OK(ensure(h->aux1, n_pairs * 8));
-  L_TRY(hipMemcpyAsync(h->aux2.p, pair_slot, n_pairs * 4,
+  U_OK(ensure(h->aux2, n_pairs * 4));
+  U_OK(ensure(h->aux1, n_pairs * 8));
+  U_TRY(hipMemcpyAsync(h->aux2.p, pair_slot, n_pairs * 4,
                        hipMemcpyHostToDevice, h->stream));
-  L_TRY(hipMemcpyAsync(h->aux1.p, new_label, n_pairs * 8,
+  U_TRY(hipMemcpyAsync(h->aux1.p, new_label, n_pairs * 8,
                        hipMemcpyHostToDevice, h->stream));
-  L_OK(ensure(h->out, h->n * h->elem_bytes));
-  L_OK(start_timer(h));
+  U_OK(ensure(h->out, h->n * h->elem_bytes));
+  U_OK(h->timer_start());
   if (n_pairs)
     hipLaunchKernelGGL(scatter_labels_kernel, dim3((n_pairs + 255) / 256),
                        dim3(256), 0, h->stream,
@@ -743,17 +676,17 @@ int ffn_labels_apply_pair_labels(ffn_labels* h, size_t n_pairs,
                        static_cast<const u64*>(h->aux1.p), (u32)n_pairs,
                        static_cast<u64*>(h->slot_label.p));
   if (h->elem_bytes == 4)
-    L_OK(apply_impl<uint32_t>(
+    U_OK(apply_impl<uint32_t>(
         h, static_cast<const uint32_t*>(h->a.p),
         h->have_b ? static_cast<const uint32_t*>(h->b.p) : nullptr, h->n, -1,
         static_cast<uint32_t*>(h->out.p)));
   else
-    L_OK(apply_impl<uint64_t>(
+    U_OK(apply_impl<uint64_t>(
         h, static_cast<const uint64_t*>(h->a.p),
         h->have_b ? static_cast<const uint64_t*>(h->b.p) : nullptr, h->n, -1,
         static_cast<uint64_t*>(h->out.p)));
-  L_OK(stop_timer(h, (double)h->n * h->elem_bytes * (h->have_b ? 3 : 2)));
-  L_TRY(hipMemcpy(out, h->out.p, h->n * h->elem_bytes, hipMemcpyDeviceToHost));
+  U_OK(stop_timer(h, (double)h->n * h->elem_bytes * (h->have_b ? 3 : 2)));
+  U_TRY(hipMemcpy(out, h->out.p, h->n * h->elem_bytes, hipMemcpyDeviceToHost));
   return FFN_OK;
 }
 
@@ -766,21 +699,21 @@ int ffn_labels_remap(ffn_labels* h, const void* in, int elem_bytes, size_t n,
     return ffn_set_error(FFN_ERR_ARG, "elem_bytes must be 4 or 8");
   if (n_keys >= (1u << 29))
     return ffn_set_error(FFN_ERR_ARG, "too many keys");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   if (n == 0) return FFN_OK;
-  L_OK(ensure(h->small, 64));
+  U_OK(ensure(h->small, 64));
   int* overflow = static_cast<int*>(h->small.p);
   u32 nslots = table_size_for(n_keys);
-  L_OK(ensure(h->aux0, std::max<size_t>(n_keys, 1) * 8));
-  L_OK(ensure(h->aux1, std::max<size_t>(n_keys, 1) * 8));
-  L_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
+  U_OK(ensure(h->aux0, std::max<size_t>(n_keys, 1) * 8));
+  U_OK(ensure(h->aux1, std::max<size_t>(n_keys, 1) * 8));
+  U_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
-  L_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
+  U_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
   for (;;) {
-    L_OK(alloc_table(h, nslots, false));
-    L_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+    U_OK(alloc_table(h, nslots, false));
+    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
     if (n_keys)
       hipLaunchKernelGGL(map_build_kernel, dim3((n_keys + 255) / 256),
                          dim3(256), 0, h->stream,
@@ -789,11 +722,11 @@ int ffn_labels_remap(ffn_labels* h, const void* in, int elem_bytes, size_t n,
                          static_cast<u64*>(h->keys.p),
                          static_cast<u64*>(h->slot_label.p), nslots - 1,
                          overflow);
-    L_TRY(hipGetLastError());
+    U_TRY(hipGetLastError());
     int ov = 0;
-    L_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
+    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
                          h->stream));
-    L_TRY(hipStreamSynchronize(h->stream));
+    U_TRY(hipStreamSynchronize(h->stream));
     if (!ov) break;
     if (nslots >= (1u << 30))
       return ffn_set_error(FFN_ERR_ARG, "remap table overflow");
@@ -803,21 +736,21 @@ int ffn_labels_remap(ffn_labels* h, const void* in, int elem_bytes, size_t n,
   h->n = n;
   h->elem_bytes = elem_bytes;
   h->have_b = false;
-  L_OK(ensure(h->a, n * elem_bytes));
-  L_OK(ensure(h->out, n * elem_bytes));
-  L_TRY(hipMemcpyAsync(h->a.p, in, n * elem_bytes, hipMemcpyHostToDevice,
+  U_OK(ensure(h->a, n * elem_bytes));
+  U_OK(ensure(h->out, n * elem_bytes));
+  U_TRY(hipMemcpyAsync(h->a.p, in, n * elem_bytes, hipMemcpyHostToDevice,
                        h->stream));
-  L_OK(start_timer(h));
+  U_OK(h->timer_start());
   if (elem_bytes == 4)
-    L_OK(apply_impl<uint32_t>(h, static_cast<const uint32_t*>(h->a.p), nullptr,
+    U_OK(apply_impl<uint32_t>(h, static_cast<const uint32_t*>(h->a.p), nullptr,
                               n, keep_missing ? 1 : 0,
                               static_cast<uint32_t*>(h->out.p)));
   else
-    L_OK(apply_impl<uint64_t>(h, static_cast<const uint64_t*>(h->a.p), nullptr,
+    U_OK(apply_impl<uint64_t>(h, static_cast<const uint64_t*>(h->a.p), nullptr,
                               n, keep_missing ? 1 : 0,
                               static_cast<uint64_t*>(h->out.p)));
-  L_OK(stop_timer(h, (double)n * elem_bytes * 2));
-  L_TRY(hipMemcpy(out, h->out.p, n * elem_bytes, hipMemcpyDeviceToHost));
+  U_OK(stop_timer(h, (double)n * elem_bytes * 2));
+  U_TRY(hipMemcpy(out, h->out.p, n * elem_bytes, hipMemcpyDeviceToHost));
   return FFN_OK;
 }
 
@@ -843,7 +776,7 @@ int ffn_labels_connected_components(ffn_labels* h, const void* in,
   const u32 n = (u32)(shape_zyx[0] * shape_zyx[1] * shape_zyx[2]);
   *n_components = 0;
   if (first_zero_index) *first_zero_index = -1;
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   if (n == 0) return FFN_OK;
   if (!in || !out) return ffn_set_error(FFN_ERR_ARG, "NULL volume");
@@ -864,32 +797,32 @@ int ffn_labels_connected_components(ffn_labels* h, const void* in,
         ++g.n_off;
       }
   const u32 ntiles = (n + kScanTile - 1) / kScanTile;
-  L_OK(ensure(h->a, (size_t)n * elem_bytes));
-  L_OK(ensure(h->out, (size_t)n * elem_bytes));
-  L_OK(ensure(h->aux0, (size_t)n * 4));
-  L_OK(ensure(h->aux1, (size_t)n * 4));
-  L_OK(ensure(h->aux2, (size_t)ntiles * 4));
-  L_OK(ensure(h->small, 64));
-  if (first_index) L_OK(ensure(h->keys, std::max<size_t>(cap, 1) * 8));
-  if (sizes) L_OK(ensure(h->counts, std::max<size_t>(cap, 1) * 8));
-  L_TRY(hipMemcpyAsync(h->a.p, in, (size_t)n * elem_bytes,
+  U_OK(ensure(h->a, (size_t)n * elem_bytes));
+  U_OK(ensure(h->out, (size_t)n * elem_bytes));
+  U_OK(ensure(h->aux0, (size_t)n * 4));
+  U_OK(ensure(h->aux1, (size_t)n * 4));
+  U_OK(ensure(h->aux2, (size_t)ntiles * 4));
+  U_OK(ensure(h->small, 64));
+  if (first_index) U_OK(ensure(h->keys, std::max<size_t>(cap, 1) * 8));
+  if (sizes) U_OK(ensure(h->counts, std::max<size_t>(cap, 1) * 8));
+  U_TRY(hipMemcpyAsync(h->a.p, in, (size_t)n * elem_bytes,
                        hipMemcpyHostToDevice, h->stream));
   if (elem_bytes == 4)
-    L_OK(cc_impl<uint32_t>(h, n, g, cap, n_components, first_index != nullptr,
+    U_OK(cc_impl<uint32_t>(h, n, g, cap, n_components, first_index != nullptr,
                            sizes != nullptr));
   else
-    L_OK(cc_impl<uint64_t>(h, n, g, cap, n_components, first_index != nullptr,
+    U_OK(cc_impl<uint64_t>(h, n, g, cap, n_components, first_index != nullptr,
                            sizes != nullptr));
   u32 fz = 0;
-  L_TRY(hipMemcpy(&fz, h->small.p, 4, hipMemcpyDeviceToHost));
+  U_TRY(hipMemcpy(&fz, h->small.p, 4, hipMemcpyDeviceToHost));
   if (first_zero_index) *first_zero_index = fz == kBackground ? -1 : (int64_t)fz;
-  L_TRY(hipMemcpy(out, h->out.p, (size_t)n * elem_bytes,
+  U_TRY(hipMemcpy(out, h->out.p, (size_t)n * elem_bytes,
                   hipMemcpyDeviceToHost));
   const size_t ncopy = std::min<size_t>(cap, *n_components);
   if (first_index && ncopy)
-    L_TRY(hipMemcpy(first_index, h->keys.p, ncopy * 8, hipMemcpyDeviceToHost));
+    U_TRY(hipMemcpy(first_index, h->keys.p, ncopy * 8, hipMemcpyDeviceToHost));
   if (sizes && ncopy)
-    L_TRY(hipMemcpy(sizes, h->counts.p, ncopy * 8, hipMemcpyDeviceToHost));
+    U_TRY(hipMemcpy(sizes, h->counts.p, ncopy * 8, hipMemcpyDeviceToHost));
   if ((first_index || sizes) && *n_components > cap)
     return ffn_set_error(FFN_ERR_ARG, "%llu components exceed cap %zu",
                          (unsigned long long)*n_components, cap);
@@ -918,25 +851,25 @@ int ffn_labels_copy_device(ffn_labels* h, const int32_t* src_dev, size_t n,
                            int32_t* dst_dev) {
   if (!h || (n && (!src_dev || !dst_dev)))
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   if (n)
     hipLaunchKernelGGL(copy_labels_kernel, dim3(grid_for(n, kThreads * 8)),
                        dim3(kThreads), 0, h->stream, src_dev, n, dst_dev);
-  L_TRY(hipGetLastError());
-  L_TRY(hipStreamSynchronize(h->stream));
+  U_TRY(hipGetLastError());
+  U_TRY(hipStreamSynchronize(h->stream));
   return FFN_OK;
 }
 
 int ffn_labels_copy_canvas(ffn_labels* h, ffn_canvas* canvas, int32_t* dst_dev) {
   if (!h || !canvas || !dst_dev) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   FfnCanvasView v;
-  L_OK(ffn_canvas_view(canvas, &v));
+  U_OK(ffn_canvas_view(canvas, &v));
   if (v.device_id != h->device_id)
     return ffn_set_error(FFN_ERR_ARG, "canvas lives on device %d, labels on %d",
                          v.device_id, h->device_id);
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   // the canvas' own stream may still be committing the last segment
-  L_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
+  U_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
   const size_t n = (size_t)v.shape_zyx[0] * v.shape_zyx[1] * v.shape_zyx[2];
   return ffn_labels_copy_device(h, v.segmentation, n, dst_dev);
 }
@@ -950,16 +883,16 @@ int ffn_labels_place_core_device(ffn_labels* h, const int32_t* src_dev,
   if (!h || !src_dev || !dst_dev || !src_shape_zyx || !core_lo || !core_hi ||
       !dst_shape_zyx || !corner_zyx)
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   Box3 b;
-  L_OK(fill_box(&b, src_shape_zyx, core_lo, core_hi, dst_shape_zyx, corner_zyx));
+  U_OK(fill_box(&b, src_shape_zyx, core_lo, core_hi, dst_shape_zyx, corner_zyx));
   const long long rows = (b.hi[0] - b.lo[0]) * (b.hi[1] - b.lo[1]);
   if (rows > 0 && b.hi[2] > b.lo[2])
     hipLaunchKernelGGL(place_core_kernel,
                        dim3((unsigned)std::min<long long>(rows, 1 << 20)),
                        dim3(kThreads), 0, h->stream, src_dev, id_offset, dst_dev, b);
-  L_TRY(hipGetLastError());
-  L_TRY(hipStreamSynchronize(h->stream));
+  U_TRY(hipGetLastError());
+  U_TRY(hipStreamSynchronize(h->stream));
   return FFN_OK;
 }
 
@@ -976,9 +909,9 @@ int ffn_labels_margin_pairs_device(ffn_labels* h, const int32_t* own_dev,
       !core_hi || !assembled_shape_zyx || !corner_zyx || !pair_a || !pair_b ||
       !pair_count || !n_pairs)
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   Box3 b;
-  L_OK(fill_box(&b, own_shape_zyx, core_lo, core_hi, assembled_shape_zyx,
+  U_OK(fill_box(&b, own_shape_zyx, core_lo, core_hi, assembled_shape_zyx,
                 corner_zyx));
   const size_t n = (size_t)own_shape_zyx[0] * own_shape_zyx[1] * own_shape_zyx[2];
   h->pairs_valid = false;
@@ -987,15 +920,15 @@ int ffn_labels_margin_pairs_device(ffn_labels* h, const int32_t* own_dev,
   h->n = n;
   h->elem_bytes = 4;
   h->have_b = true;
-  L_OK(ensure(h->a, n * 4));
-  L_OK(ensure(h->b, n * 4));
+  U_OK(ensure(h->a, n * 4));
+  U_OK(ensure(h->b, n * 4));
   const long long rows = own_shape_zyx[0] * own_shape_zyx[1];
   hipLaunchKernelGGL(margin_gather_kernel,
                      dim3((unsigned)std::min<long long>(rows, 1 << 20)),
                      dim3(kThreads), 0, h->stream, own_dev, id_offset,
                      assembled_dev, static_cast<u32*>(h->a.p),
                      static_cast<u32*>(h->b.p), b);
-  L_TRY(hipGetLastError());
+  U_TRY(hipGetLastError());
   std::vector<uint32_t> slots(cap ? cap : 1);
   return pair_counts_impl<uint32_t>(h, n, cap, pair_a, pair_b, pair_count,
                                     slots.data(), n_pairs);
@@ -1007,31 +940,31 @@ int ffn_labels_remap_device(ffn_labels* h, int32_t* vol_dev, size_t n,
   if (!h || (n && !vol_dev) || (n_keys && (!keys || !values)))
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   if (n_keys >= (1u << 29)) return ffn_set_error(FFN_ERR_ARG, "too many keys");
-  L_TRY(hipSetDevice(h->device_id));
+  U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   if (n == 0 || n_keys == 0) return FFN_OK;
-  L_OK(ensure(h->small, 64));
+  U_OK(ensure(h->small, 64));
   int* overflow = static_cast<int*>(h->small.p);
   u32 nslots = table_size_for(n_keys);
-  L_OK(ensure(h->aux0, n_keys * 8));
-  L_OK(ensure(h->aux1, n_keys * 8));
-  L_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
+  U_OK(ensure(h->aux0, n_keys * 8));
+  U_OK(ensure(h->aux1, n_keys * 8));
+  U_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
-  L_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
+  U_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
   for (;;) {
-    L_OK(alloc_table(h, nslots, false));
-    L_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+    U_OK(alloc_table(h, nslots, false));
+    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
     hipLaunchKernelGGL(map_build_kernel, dim3((n_keys + 255) / 256), dim3(256), 0,
                        h->stream, static_cast<const u64*>(h->aux0.p),
                        static_cast<const u64*>(h->aux1.p), (u32)n_keys,
                        static_cast<u64*>(h->keys.p),
                        static_cast<u64*>(h->slot_label.p), nslots - 1, overflow);
-    L_TRY(hipGetLastError());
+    U_TRY(hipGetLastError());
     int ov = 0;
-    L_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
+    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
                          h->stream));
-    L_TRY(hipStreamSynchronize(h->stream));
+    U_TRY(hipStreamSynchronize(h->stream));
     if (!ov) break;
     if (nslots >= (1u << 30))
       return ffn_set_error(FFN_ERR_ARG, "remap table overflow");
@@ -1041,11 +974,11 @@ int ffn_labels_remap_device(ffn_labels* h, int32_t* vol_dev, size_t n,
   h->n = n;
   h->elem_bytes = 4;
   h->have_b = false;
-  L_OK(start_timer(h));
+  U_OK(h->timer_start());
   // in place: every voxel reads its own label and writes its own slot
-  L_OK(apply_impl<uint32_t>(h, reinterpret_cast<const uint32_t*>(vol_dev), nullptr,
+  U_OK(apply_impl<uint32_t>(h, reinterpret_cast<const uint32_t*>(vol_dev), nullptr,
                             n, 1, reinterpret_cast<uint32_t*>(vol_dev)));
-  L_OK(stop_timer(h, (double)n * 4 * 2));
+  U_OK(stop_timer(h, (double)n * 4 * 2));
   return FFN_OK;
 }
 

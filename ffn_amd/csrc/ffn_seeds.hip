@@ -16,6 +16,7 @@
 
 #include "../../include/ffn_seeds.h"
 #include "ffn_internal.h"
+#include "ffn_unit.h"
 
 namespace {
 
@@ -321,19 +322,14 @@ __global__ __launch_bounds__(kThreads) void peaks_kernel(
   }
 }
 
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
+using ffn_unit::DevBuf;
+using ffn_unit::ensure;
 
 }  // namespace
 
-struct ffn_seeder {
-  int device_id = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  Buf image, fa, fb, edges, thresh, dt, filt, mask, force, d2a, d2b, val, ma,
-      mb, vstack, zstack, coords, small, weights, noise, canvas_f32;
+struct ffn_seeder : ffn_unit::Unit {
+  DevBuf image, fa, fb, edges, thresh, dt, filt, mask, force, d2a, d2b, val,
+      ma, mb, vstack, zstack, coords, small, weights, noise, canvas_f32;
   size_t noise_n = 0;
   int radius = -1;
   size_t last_n = 0;
@@ -341,29 +337,6 @@ struct ffn_seeder {
 };
 
 namespace {
-
-#define S_TRY(expr)                                                           \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess)                                                     \
-      return ffn_set_error(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,       \
-                           hipGetErrorString(_e), __FILE__, __LINE__);        \
-  } while (0)
-#define S_OK(expr)                 \
-  do {                             \
-    int _rc = (expr);              \
-    if (_rc != FFN_OK) return _rc; \
-  } while (0)
-
-int ensure(Buf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return FFN_OK;
-  if (b.p) S_TRY(hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  S_TRY(hipMalloc(&b.p, bytes ? bytes : 16));
-  b.bytes = bytes ? bytes : 16;
-  return FFN_OK;
-}
 
 inline dim3 grid_for(size_t n) {
   return dim3((unsigned)((n + kThreads - 1) / kThreads));
@@ -382,14 +355,14 @@ int run_peaks(ffn_seeder* s, const float* d_image, const uint8_t* exclude_u8,
     return ffn_set_error(FFN_ERR_STATE,
                          "noise holds %zu values, volume needs %zu",
                          s->noise_n, n);
-  for (Buf* b : {&s->fa, &s->fb, &s->edges, &s->thresh, &s->dt})
-    S_OK(ensure(*b, n * sizeof(float)));
-  S_OK(ensure(s->filt, n));
-  for (Buf* b : {&s->d2a, &s->d2b, &s->val, &s->ma, &s->mb, &s->zstack})
-    S_OK(ensure(*b, n * sizeof(double)));
-  S_OK(ensure(s->vstack, n * sizeof(int)));
-  S_OK(ensure(s->coords, std::max<size_t>(cap, 1) * 3 * sizeof(int32_t)));
-  S_OK(ensure(s->small, 64));
+  for (DevBuf* b : {&s->fa, &s->fb, &s->edges, &s->thresh, &s->dt})
+    U_OK(ensure(*b, n * sizeof(float)));
+  U_OK(ensure(s->filt, n));
+  for (DevBuf* b : {&s->d2a, &s->d2b, &s->val, &s->ma, &s->mb, &s->zstack})
+    U_OK(ensure(*b, n * sizeof(double)));
+  U_OK(ensure(s->vstack, n * sizeof(int)));
+  U_OK(ensure(s->coords, std::max<size_t>(cap, 1) * 3 * sizeof(int32_t)));
+  U_OK(ensure(s->small, 64));
   float* fa = static_cast<float*>(s->fa.p);
   float* fb = static_cast<float*>(s->fb.p);
   float* edges = static_cast<float*>(s->edges.p);
@@ -406,8 +379,8 @@ int run_peaks(ffn_seeder* s, const float* d_image, const uint8_t* exclude_u8,
   hipStream_t st = s->stream;
   const dim3 g = grid_for(n), b(kThreads);
 
-  S_TRY(hipMemsetAsync(s->small.p, 0, 64, st));
-  S_TRY(hipEventRecord(s->ev0, st));
+  U_TRY(hipMemsetAsync(s->small.p, 0, 64, st));
+  U_OK(s->timer_start());
   // -- Sobel gradient magnitude (generic_gradient_magnitude + sobel) ----------
   for (int axis = 0; axis < 3; ++axis) {
     hipLaunchKernelGGL(tap3_kernel, g, b, 0, st, d_image, fa, sh, n, axis, 0.0,
@@ -459,13 +432,13 @@ int run_peaks(ffn_seeder* s, const float* d_image, const uint8_t* exclude_u8,
   hipLaunchKernelGGL(peaks_kernel, g, b, 0, st, (const double*)val,
                      (const double*)ma, sh, n, 3,
                      static_cast<int32_t*>(s->coords.p), (unsigned)cap, count);
-  S_TRY(hipGetLastError());
-  S_TRY(hipEventRecord(s->ev1, st));
+  U_TRY(hipGetLastError());
+  U_TRY(hipEventRecord(s->ev1, st));
   int host[2] = {0, 0};
-  S_TRY(hipMemcpyAsync(host, s->small.p, 8, hipMemcpyDeviceToHost, st));
-  S_TRY(hipStreamSynchronize(st));
+  U_TRY(hipMemcpyAsync(host, s->small.p, 8, hipMemcpyDeviceToHost, st));
+  U_TRY(hipStreamSynchronize(st));
   float ms = 0.f;
-  S_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  U_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
   s->last_ms = ms;
   s->last_n = n;
   if (all_edges) *all_edges = host[0] ? 0 : 1;
@@ -478,7 +451,7 @@ int run_peaks(ffn_seeder* s, const float* d_image, const uint8_t* exclude_u8,
   if (found > cap)
     return ffn_set_error(FFN_ERR_ARG, "%u peaks exceed cap %zu", found, cap);
   if (found)
-    S_TRY(hipMemcpy(coords_zyx, s->coords.p, (size_t)found * 3 * sizeof(int32_t),
+    U_TRY(hipMemcpy(coords_zyx, s->coords.p, (size_t)found * 3 * sizeof(int32_t),
                     hipMemcpyDeviceToHost));
   return FFN_OK;
 }
@@ -502,49 +475,17 @@ int check_shape(const int64_t shape_zyx[3], size_t* n) {
 extern "C" {
 
 int ffn_seeder_create(int device_id, ffn_seeder** out) {
-  if (!out) return ffn_set_error(FFN_ERR_ARG, "out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  S_TRY(hipGetDeviceCount(&ndev));
-  if (device_id < 0 || device_id >= ndev)
-    return ffn_set_error(FFN_ERR_ARG, "device %d not present (%d devices)",
-                         device_id, ndev);
-  S_TRY(hipSetDevice(device_id));
-  ffn_seeder* s = new ffn_seeder();
-  s->device_id = device_id;
-  hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreate(&s->ev0);
-  if (e == hipSuccess) e = hipEventCreate(&s->ev1);
-  if (e != hipSuccess) {
-    ffn_seeder_destroy(s);
-    return ffn_set_error(FFN_ERR_HIP, "stream/event creation failed: %s",
-                         hipGetErrorString(e));
-  }
-  *out = s;
-  return FFN_OK;
+  return ffn_unit::unit_create(device_id, out);
 }
 
-void ffn_seeder_destroy(ffn_seeder* s) {
-  if (!s) return;
-  (void)hipSetDevice(s->device_id);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (Buf* b : {&s->image, &s->fa, &s->fb, &s->edges, &s->thresh, &s->dt,
-                 &s->filt, &s->mask, &s->force, &s->d2a, &s->d2b, &s->val,
-                 &s->ma, &s->mb, &s->vstack, &s->zstack, &s->coords, &s->small,
-                 &s->weights, &s->noise, &s->canvas_f32})
-    if (b->p) (void)hipFree(b->p);
-  if (s->ev0) (void)hipEventDestroy(s->ev0);
-  if (s->ev1) (void)hipEventDestroy(s->ev1);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
-}
+void ffn_seeder_destroy(ffn_seeder* s) { ffn_unit::unit_destroy(s); }
 
 int ffn_seeder_set_noise(ffn_seeder* s, const double* noise, size_t n) {
   if (!s || (n && !noise)) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  S_TRY(hipSetDevice(s->device_id));
-  S_OK(ensure(s->noise, n * sizeof(double)));
+  U_TRY(hipSetDevice(s->device_id));
+  U_OK(ensure(s->noise, n * sizeof(double)));
   if (n)
-    S_TRY(hipMemcpy(s->noise.p, noise, n * sizeof(double),
+    U_TRY(hipMemcpy(s->noise.p, noise, n * sizeof(double),
                     hipMemcpyHostToDevice));
   s->noise_n = n;
   return FFN_OK;
@@ -554,10 +495,10 @@ int ffn_seeder_set_gaussian(ffn_seeder* s, const double* weights, int radius) {
   if (!s || !weights) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   if (radius < 0 || radius > kMaxRadius)
     return ffn_set_error(FFN_ERR_ARG, "radius must be in [0, %d]", kMaxRadius);
-  S_TRY(hipSetDevice(s->device_id));
+  U_TRY(hipSetDevice(s->device_id));
   const size_t bytes = (size_t)(2 * radius + 1) * sizeof(double);
-  S_OK(ensure(s->weights, bytes));
-  S_TRY(hipMemcpy(s->weights.p, weights, bytes, hipMemcpyHostToDevice));
+  U_OK(ensure(s->weights, bytes));
+  U_TRY(hipMemcpy(s->weights.p, weights, bytes, hipMemcpyHostToDevice));
   s->radius = radius;
   return FFN_OK;
 }
@@ -569,19 +510,19 @@ int ffn_seeder_peaks(ffn_seeder* s, const float* image, const uint8_t* exclude,
   if (!s || !image || !voxel_size_zyx || !n_peaks || (cap && !coords_zyx))
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   size_t n = 0;
-  S_OK(check_shape(shape_zyx, &n));
-  S_TRY(hipSetDevice(s->device_id));
-  S_OK(ensure(s->image, n * sizeof(float)));
-  S_TRY(hipMemcpyAsync(s->image.p, image, n * sizeof(float),
+  U_OK(check_shape(shape_zyx, &n));
+  U_TRY(hipSetDevice(s->device_id));
+  U_OK(ensure(s->image, n * sizeof(float)));
+  U_TRY(hipMemcpyAsync(s->image.p, image, n * sizeof(float),
                        hipMemcpyHostToDevice, s->stream));
   if (exclude) {
-    S_OK(ensure(s->mask, n));
-    S_TRY(hipMemcpyAsync(s->mask.p, exclude, n, hipMemcpyHostToDevice,
+    U_OK(ensure(s->mask, n));
+    U_TRY(hipMemcpyAsync(s->mask.p, exclude, n, hipMemcpyHostToDevice,
                          s->stream));
   }
   if (force_edge) {
-    S_OK(ensure(s->force, n));
-    S_TRY(hipMemcpyAsync(s->force.p, force_edge, n, hipMemcpyHostToDevice,
+    U_OK(ensure(s->force, n));
+    U_TRY(hipMemcpyAsync(s->force.p, force_edge, n, hipMemcpyHostToDevice,
                          s->stream));
   }
   return run_peaks(s, static_cast<const float*>(s->image.p),
@@ -600,21 +541,21 @@ int ffn_seeder_peaks_canvas(ffn_seeder* s, ffn_canvas* canvas,
   if (!s || !canvas || !voxel_size_zyx || !n_peaks || (cap && !coords_zyx))
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   FfnCanvasView v;
-  S_OK(ffn_canvas_view(canvas, &v));
+  U_OK(ffn_canvas_view(canvas, &v));
   if (v.device_id != s->device_id)
     return ffn_set_error(FFN_ERR_ARG, "canvas lives on device %d, seeder on %d",
                          v.device_id, s->device_id);
-  S_TRY(hipSetDevice(s->device_id));
+  U_TRY(hipSetDevice(s->device_id));
   // the canvas' own stream may still be pasting / committing
-  S_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
+  U_TRY(hipStreamSynchronize(static_cast<hipStream_t>(v.engine_stream)));
   const int64_t shape[3] = {v.shape_zyx[0], v.shape_zyx[1], v.shape_zyx[2]};
   size_t n = 0;
-  S_OK(check_shape(shape, &n));
+  U_OK(check_shape(shape, &n));
   const float* image = v.image;
   if (!image) {
     // uint8 canvas: PolicyPeaks works on the normalised f32 image (seed.py:146);
     // materialise it for the duration of this call only
-    S_OK(ensure(s->canvas_f32, n * sizeof(float)));
+    U_OK(ensure(s->canvas_f32, n * sizeof(float)));
     hipLaunchKernelGGL(lut_u8_kernel, grid_for(n), dim3(kThreads), 0, s->stream,
                        v.image_u8, v.image_lut,
                        static_cast<float*>(s->canvas_f32.p), n);
@@ -630,19 +571,19 @@ int ffn_seeder_edt(ffn_seeder* s, const uint8_t* mask,
   if (!s || !mask || !voxel_size_zyx || !dist)
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   size_t n = 0;
-  S_OK(check_shape(shape_zyx, &n));
-  S_TRY(hipSetDevice(s->device_id));
+  U_OK(check_shape(shape_zyx, &n));
+  U_TRY(hipSetDevice(s->device_id));
   const Shape sh{(int)shape_zyx[0], (int)shape_zyx[1], (int)shape_zyx[2]};
-  S_OK(ensure(s->mask, n));
-  S_OK(ensure(s->filt, n));
-  S_OK(ensure(s->d2a, n * sizeof(double)));
-  S_OK(ensure(s->d2b, n * sizeof(double)));
-  S_OK(ensure(s->zstack, n * sizeof(double)));
-  S_OK(ensure(s->vstack, n * sizeof(int)));
+  U_OK(ensure(s->mask, n));
+  U_OK(ensure(s->filt, n));
+  U_OK(ensure(s->d2a, n * sizeof(double)));
+  U_OK(ensure(s->d2b, n * sizeof(double)));
+  U_OK(ensure(s->zstack, n * sizeof(double)));
+  U_OK(ensure(s->vstack, n * sizeof(int)));
   hipStream_t st = s->stream;
   const dim3 b(kThreads);
-  S_TRY(hipMemcpyAsync(s->mask.p, mask, n, hipMemcpyHostToDevice, st));
-  S_TRY(hipEventRecord(s->ev0, st));
+  U_TRY(hipMemcpyAsync(s->mask.p, mask, n, hipMemcpyHostToDevice, st));
+  U_OK(s->timer_start());
   hipLaunchKernelGGL(mask_to_features_kernel, grid_for(n), b, 0, st,
                      static_cast<const uint8_t*>(s->mask.p),
                      static_cast<uint8_t*>(s->filt.p), n);
@@ -663,12 +604,12 @@ int ffn_seeder_edt(ffn_seeder* s, const uint8_t* mask,
                      static_cast<int*>(s->vstack.p),
                      static_cast<double*>(s->zstack.p), zlines);
   hipLaunchKernelGGL(sqrt_kernel, grid_for(n), b, 0, st, d2a, n);
-  S_TRY(hipGetLastError());
-  S_TRY(hipEventRecord(s->ev1, st));
-  S_TRY(hipMemcpyAsync(dist, d2a, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  S_TRY(hipStreamSynchronize(st));
+  U_TRY(hipGetLastError());
+  U_TRY(hipEventRecord(s->ev1, st));
+  U_TRY(hipMemcpyAsync(dist, d2a, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  U_TRY(hipStreamSynchronize(st));
   float ms = 0.f;
-  S_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  U_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
   s->last_ms = ms;
   s->last_n = 0;  // no peaks stages to read back
   return FFN_OK;
@@ -677,11 +618,11 @@ int ffn_seeder_edt(ffn_seeder* s, const uint8_t* mask,
 int ffn_seeder_read_stage(ffn_seeder* s, int which, float* dst) {
   if (!s || !dst) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   if (!s->last_n) return ffn_set_error(FFN_ERR_STATE, "no peaks call yet");
-  const Buf* b = which == 0 ? &s->edges : which == 1 ? &s->thresh
-                 : which == 2 ? &s->dt : nullptr;
+  const DevBuf* b = which == 0 ? &s->edges : which == 1 ? &s->thresh
+                    : which == 2 ? &s->dt : nullptr;
   if (!b) return ffn_set_error(FFN_ERR_ARG, "which must be 0, 1 or 2");
-  S_TRY(hipSetDevice(s->device_id));
-  S_TRY(hipMemcpy(dst, b->p, s->last_n * sizeof(float), hipMemcpyDeviceToHost));
+  U_TRY(hipSetDevice(s->device_id));
+  U_TRY(hipMemcpy(dst, b->p, s->last_n * sizeof(float), hipMemcpyDeviceToHost));
   return FFN_OK;
 }
 

@@ -16,6 +16,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from . import _unit
 from ._lib import check
 
 _MAX_UINT32 = 2**32 - 1
@@ -32,31 +33,17 @@ def _i64x3(v):
   return (ctypes.c_int64 * 3)(*[int(x) for x in v])
 
 
-class DecisionOps:
+class DecisionOps(_unit.Handle):
   """One stream + grow-only device scratch for the decision point kernels."""
 
   def __init__(self, device_id: int = 0):
-    self._lib = _lib.load()
-    self._h = ctypes.c_void_p()
-    self.device_id = int(device_id)
-    check(self._lib.ffn_decision_create(self.device_id, ctypes.byref(self._h)))
+    super().__init__('ffn_decision_create', 'ffn_decision_destroy', device_id)
     self.lock = threading.Lock()
     self._shape = None   # of the resident expansion
     self._values = None  # original ids of a remapped (>= 2**32 - 1) input
     self._dtype = np.dtype(np.uint32)
     #: first output capacity of contact_minima (grown on demand)
     self.initial_cap = 1 << 16
-
-  def close(self):
-    if self._h:
-      self._lib.ffn_decision_destroy(self._h)
-      self._h = ctypes.c_void_p()
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
 
   # -- stage 1: expansion ---------------------------------------------------------
   @staticmethod
@@ -160,8 +147,8 @@ class DecisionOps:
     lo = hi = None
     if sub_box is not None:
       lo, hi = _i64x3(sub_box[0]), _i64x3(sub_box[1])
-    cap = max(int(self.initial_cap), 1)
-    while True:
+
+    def call(cap):
       pa = np.empty(cap, np.uint64)
       pb = np.empty(cap, np.uint64)
       dist = np.empty(cap, np.float64)
@@ -170,12 +157,10 @@ class DecisionOps:
       rc = self._lib.ffn_decision_contact_minima(
           self._h, lo, hi, cap, pa.ctypes.data, pb.ctypes.data,
           dist.ctypes.data, off.ctypes.data, ctypes.byref(found))
-      if rc != 0 and found.value > cap:
-        cap = found.value
-        continue
-      check(rc)
-      break
-    m = found.value
+      return rc, found, (pa, pb, dist, off)
+
+    m, (pa, pb, dist, off) = _unit.grow_until_fits(
+        call, max(int(self.initial_cap), 1))
     return {'a': self._ids(pa[:m]).astype(np.uint64),
             'b': self._ids(pb[:m]).astype(np.uint64),
             'dist': dist[:m], 'off': off[:m, 0].copy(), 'z': off[:m, 1].copy(),
@@ -189,29 +174,9 @@ class DecisionOps:
     return (ms[0], nbytes[0]), (ms[1], nbytes[1])
 
 
-_default = {}
-_default_lock = threading.Lock()
+_default = _unit.Registry(DecisionOps)
 
 
 def default_ops(device_id: int = 0) -> DecisionOps:
   """Process-wide DecisionOps of a device (created on first use)."""
-  with _default_lock:
-    ops = _default.get(device_id)
-    if ops is None:
-      ops = DecisionOps(device_id)
-      _default[device_id] = ops
-    return ops
-
-
-import atexit  # pylint:disable=wrong-import-position
-
-
-@atexit.register
-def _close_default_ops():
-  # release device objects while the HIP runtime is still alive
-  for ops in list(_default.values()):
-    try:
-      ops.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
-  _default.clear()
+  return _default.get(device_id)

@@ -15,6 +15,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib
+from . import _unit
 from ._lib import check
 
 
@@ -28,27 +29,13 @@ def _as_labels(arr: np.ndarray) -> np.ndarray:
   return np.ascontiguousarray(arr)
 
 
-class LabelOps:
+class LabelOps(_unit.Handle):
   """One stream + grow-only device scratch for label kernels on one GPU."""
 
   def __init__(self, device_id: int = 0):
-    self._lib = _lib.load()
-    self._h = ctypes.c_void_p()
-    self.device_id = int(device_id)
-    check(self._lib.ffn_labels_create(self.device_id, ctypes.byref(self._h)))
+    super().__init__('ffn_labels_create', 'ffn_labels_destroy', device_id)
     self._lock = threading.Lock()
     self._resident = None  # (shape, dtype) of the volumes of the pair table
-
-  def close(self):
-    if self._h:
-      self._lib.ffn_labels_destroy(self._h)
-      self._h = ctypes.c_void_p()
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
 
   # -- joint histogram + relabel by pair ---------------------------------------
   def pair_counts(self, a: np.ndarray, b: Optional[np.ndarray] = None):
@@ -66,8 +53,8 @@ class LabelOps:
         wide = np.uint64 if 8 in (a.dtype.itemsize, b.dtype.itemsize) else None
         a, b = a.astype(wide), b.astype(wide)
     n = a.size
-    cap = max(min(n, 1 << 22), 1)
-    while True:
+
+    def call(cap):
       pa = np.empty(cap, np.uint64)
       pb = np.empty(cap, np.uint64)
       pc = np.empty(cap, np.uint64)
@@ -77,12 +64,9 @@ class LabelOps:
           self._h, a.ctypes.data, b.ctypes.data if b is not None else None,
           a.dtype.itemsize, n, cap, pa.ctypes.data, pb.ctypes.data,
           pc.ctypes.data, ps.ctypes.data, ctypes.byref(found))
-      if rc != 0 and found.value > cap:
-        cap = found.value
-        continue
-      check(rc)
-      break
-    m = found.value
+      return rc, found, (pa, pb, pc, ps)
+
+    m, (pa, pb, pc, ps) = _unit.grow_until_fits(call, max(min(n, 1 << 22), 1))
     self._resident = (a.shape, a.dtype)
     return pa[:m], pb[:m], pc[:m], ps[:m]
 
@@ -130,8 +114,8 @@ class LabelOps:
     shape = (ctypes.c_int64 * 3)(*src.shape)
     ncomp = ctypes.c_uint64(0)
     fz = ctypes.c_int64(-1)
-    cap = 1 << 20 if stats else 0
-    while True:
+
+    def call(cap):
       first = np.empty(max(cap, 1), np.uint64) if stats else None
       sizes = np.empty(max(cap, 1), np.uint64) if stats else None
       rc = self._lib.ffn_labels_connected_components(
@@ -139,15 +123,13 @@ class LabelOps:
           int(connectivity), out.ctypes.data, ctypes.byref(ncomp), cap,
           first.ctypes.data if stats else None,
           sizes.ctypes.data if stats else None, ctypes.byref(fz))
-      if rc != 0 and stats and ncomp.value > cap:
-        cap = int(ncomp.value)
-        continue
-      check(rc)
-      break
+      # only the stats arrays can be too small
+      return rc, ncomp if stats else ctypes.c_uint64(0), (first, sizes)
+
+    k, (first, sizes) = _unit.grow_until_fits(call, 1 << 20 if stats else 0)
     self._resident = None
     if not stats:
       return out
-    k = int(ncomp.value)
     return out, first[:k], sizes[:k], int(fz.value)
 
   # -- device-resident assembly (raw device pointers, int32 labels) ----------------
@@ -177,8 +159,8 @@ class LabelOps:
   def margin_pairs_device(self, own_ptr, own_shape, id_offset, core_lo, core_hi,
                           assembled_ptr, assembled_shape, corner):
     """(own id + offset, assembled id, voxels) over a sub-box's margin."""
-    cap = 1 << 16
-    while True:
+
+    def call(cap):
       pa = np.empty(cap, np.uint64)
       pb = np.empty(cap, np.uint64)
       pc = np.empty(cap, np.uint64)
@@ -189,13 +171,10 @@ class LabelOps:
           ctypes.c_void_p(assembled_ptr), self._i64x3(assembled_shape),
           self._i64x3(corner), cap, pa.ctypes.data, pb.ctypes.data,
           pc.ctypes.data, ctypes.byref(found))
-      if rc != 0 and found.value > cap:
-        cap = found.value
-        continue
-      check(rc)
-      break
+      return rc, found, (pa, pb, pc)
+
+    m, (pa, pb, pc) = _unit.grow_until_fits(call, 1 << 16)
     self._resident = None
-    m = found.value
     return pa[:m], pb[:m], pc[:m]
 
   def remap_device(self, vol_ptr: int, n: int, keys, values):
@@ -216,29 +195,9 @@ class LabelOps:
     return ms.value, nbytes.value
 
 
-_default = {}
-_default_lock = threading.Lock()
+_default = _unit.Registry(LabelOps)
 
 
 def default_ops(device_id: int = 0) -> LabelOps:
   """Process-wide LabelOps of a device (created on first use)."""
-  with _default_lock:
-    ops = _default.get(device_id)
-    if ops is None:
-      ops = LabelOps(device_id)
-      _default[device_id] = ops
-    return ops
-
-
-import atexit  # pylint:disable=wrong-import-position
-
-
-@atexit.register
-def _close_default_ops():
-  # release device objects while the HIP runtime is still alive
-  for ops in list(_default.values()):
-    try:
-      ops.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
-  _default.clear()
+  return _default.get(device_id)

@@ -9,13 +9,12 @@ gaussian taps, both computed with numpy exactly as scipy does.
 
 from __future__ import annotations
 
-import atexit
 import ctypes
 import threading
 
 import numpy as np
 
-from . import _lib
+from . import _unit
 from ._lib import check
 
 SIGMA = 49.0 / 6.0  # seed.py:163
@@ -32,29 +31,15 @@ def gaussian_weights(sigma: float = SIGMA, truncate: float = 4.0):
   return np.ascontiguousarray(phi[::-1]), lw
 
 
-class Seeder:
+class Seeder(_unit.Handle):
   """One stream + grow-only device scratch for PolicyPeaks on one GPU."""
 
   def __init__(self, device_id: int = 0):
-    self._lib = _lib.load()
-    self._h = ctypes.c_void_p()
-    self.device_id = int(device_id)
-    check(self._lib.ffn_seeder_create(self.device_id, ctypes.byref(self._h)))
+    super().__init__('ffn_seeder_create', 'ffn_seeder_destroy', device_id)
     w, r = gaussian_weights()
     check(self._lib.ffn_seeder_set_gaussian(self._h, w.ctypes.data, r))
     self._noise_n = 0
     self._lock = threading.Lock()
-
-  def close(self):
-    if self._h:
-      self._lib.ffn_seeder_destroy(self._h)
-      self._h = ctypes.c_void_p()
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
 
   def _ensure_noise(self, n: int):
     if n <= self._noise_n:
@@ -66,21 +51,18 @@ class Seeder:
     self._noise_n = n
 
   def _collect(self, call, n: int):
-    cap = 1 << 16
-    while True:
+    def sized(cap):
       coords = np.empty((cap, 3), np.int32)
       found = ctypes.c_size_t(0)
       all_edges = ctypes.c_int32(0)
       rc = call(cap, coords.ctypes.data, ctypes.byref(found),
                 ctypes.byref(all_edges))
-      if rc != 0 and found.value > cap:
-        cap = int(found.value)
-        continue
-      check(rc)
-      break
+      return rc, found, (coords, all_edges)
+
+    m, (coords, all_edges) = _unit.grow_until_fits(sized, 1 << 16)
     if all_edges.value:
       return None
-    coords = coords[:found.value].astype(np.int64)
+    coords = coords[:m].astype(np.int64)
     order = np.lexsort((coords[:, 2], coords[:, 1], coords[:, 0]))
     return coords[order]  # ascending (z, y, x), seed.py:193
 
@@ -146,24 +128,8 @@ class Seeder:
     return ms.value, vox.value
 
 
-_default = {}
-_default_lock = threading.Lock()
+_default = _unit.Registry(Seeder)
 
 
 def default_seeder(device_id: int = 0) -> Seeder:
-  with _default_lock:
-    s = _default.get(device_id)
-    if s is None:
-      s = Seeder(device_id)
-      _default[device_id] = s
-    return s
-
-
-@atexit.register
-def _close_default_seeders():
-  for s in list(_default.values()):
-    try:
-      s.close()
-    except Exception:  # pylint:disable=broad-except
-      pass
-  _default.clear()
+  return _default.get(device_id)
