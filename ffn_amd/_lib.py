@@ -22,9 +22,10 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_labels.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
-           'ffn_analysis.hip']
+           'ffn_analysis.hip', 'ffn_partitions.hip']
 
 MAX_CANDIDATES = 16
 
@@ -308,6 +309,18 @@ SIGNATURES = {
              ctypes.POINTER(ctypes.c_size_t)]),
     'ffn_analyzer_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_partitions.h
+    'ffn_partitions_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_partitions_destroy': (None, [_P]),
+    'ffn_partitions_label_sizes': (_I, [_P, _P, _I,
+                                        ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_size_t, _P, _P,
+                                        ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_partitions_compute': (_I, [_P, _P, _P, ctypes.c_size_t, _I3, _P,
+                                    ctypes.c_size_t, _P, _P, ctypes.c_size_t]),
+    'ffn_partitions_read': (_I, [_P, _P, _P, _P]),
+    'ffn_partitions_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None
