@@ -23,9 +23,10 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
-           'ffn_analysis.hip', 'ffn_partitions.hip']
+           'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip']
 
 MAX_CANDIDATES = 16
 
@@ -321,6 +322,26 @@ SIGNATURES = {
     'ffn_partitions_read': (_I, [_P, _P, _P, _P]),
     'ffn_partitions_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_coordinates.h
+    'ffn_coordinates_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_coordinates_destroy': (None, [_P]),
+    'ffn_coordinates_reset': (_I, [_P]),
+    'ffn_coordinates_add_volume': (_I, [_P, _P, ctypes.POINTER(ctypes.c_int64),
+                                        _P]),
+    'ffn_coordinates_read_class': (_I, [_P, ctypes.c_size_t, _I,
+                                        ctypes.c_size_t, _P,
+                                        ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_coordinates_gather': (_I, [_P, _P, ctypes.c_size_t, ctypes.c_uint64,
+                                    _P, ctypes.c_size_t, _P, ctypes.c_size_t,
+                                    _I3]),
+    'ffn_coordinates_read': (_I, [_P, ctypes.c_size_t, ctypes.c_size_t, _P,
+                                  _P]),
+    'ffn_coordinates_set_names': (_I, [_P, _P, _P, ctypes.c_size_t]),
+    'ffn_coordinates_serialize': (_I, [_P, ctypes.c_size_t, ctypes.c_size_t,
+                                       ctypes.c_size_t, _P,
+                                       ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_coordinates_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                         ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None
