@@ -24,9 +24,11 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
-           'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip']
+           'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip',
+           'ffn_evaluation.hip']
 
 MAX_CANDIDATES = 16
 
@@ -155,6 +157,19 @@ class PairDesc(ctypes.Structure):
               ('shape_zyx', ctypes.c_int32 * 3), ('reserved', ctypes.c_int32)]
 
 
+class EvaluationGeometry(ctypes.Structure):
+  """ffn_evaluation_geometry (include/ffn_evaluation.h)."""
+  _fields_ = [('input_seed_zyx', ctypes.c_int32 * 3),
+              ('input_image_zyx', ctypes.c_int32 * 3),
+              ('pred_mask_zyx', ctypes.c_int32 * 3),
+              ('deltas_zyx', ctypes.c_int32 * 3),
+              ('canvas_zyx', ctypes.c_int32 * 3),
+              ('image_patch_zyx', ctypes.c_int32 * 3),
+              ('label_patch_zyx', ctypes.c_int32 * 3),
+              ('eval_zyx', ctypes.c_int32 * 3),
+              ('slots', ctypes.c_int32)]
+
+
 class EndpointDesc(ctypes.Structure):
   """ffn_endpoint_desc (include/ffn_analysis.h)."""
   _fields_ = [('probs', ctypes.c_void_p), ('seg', ctypes.c_void_p),
@@ -188,6 +203,7 @@ SIGNATURES = {
     'ffn_engine_debug_workgroups': (_I, [_P, _P, _I]),
     'ffn_engine_debug_flow_trace': (_I, [_P, _P, _I]),
     'ffn_predict': (_I, [_P, _I, _P, _P, _P]),
+    'ffn_predict_device': (_I, [_P, _I, _P, _P, _P]),
     'ffn_forward_resident': (_I, [_P, _I, _I]),
     'ffn_canvas_create': (_I, [_P, _P, _I3, ctypes.POINTER(_P)]),
     'ffn_canvas_create_u8': (_I, [_P, _P, _I3, ctypes.c_float, ctypes.c_float,
@@ -342,6 +358,32 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_size_t)]),
     'ffn_coordinates_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_evaluation.h
+    'ffn_evaluation_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_evaluation_destroy': (None, [_P]),
+    'ffn_evaluation_configure': (_I, [_P, ctypes.POINTER(EvaluationGeometry)]),
+    'ffn_evaluation_io_buffers': (_I, [_P, ctypes.POINTER(_P),
+                                       ctypes.POINTER(_P), ctypes.POINTER(_P)]),
+    'ffn_evaluation_reset': (_I, [_P]),
+    'ffn_evaluation_add_volume': (_I, [_P, _P, _I, _P, _I,
+                                       ctypes.POINTER(ctypes.c_int64), _I3]),
+    'ffn_evaluation_load': (_I, [_P, _I, _P, _P, _P, _P, _P, ctypes.c_float,
+                                 ctypes.c_float]),
+    'ffn_evaluation_probe_moves': (_I, [_P, ctypes.c_size_t, _P, _P,
+                                        ctypes.c_float, ctypes.c_float, _P, _P]),
+    'ffn_evaluation_gather': (_I, [_P, _I, _P, _P, _P, _P]),
+    'ffn_evaluation_paste': (_I, [_P, _I, _P, _P, _P, _I]),
+    'ffn_evaluation_score_faces': (_I, [_P, _I, _P, _P, _P, _P]),
+    'ffn_evaluation_finish': (_I, [_P, _I, ctypes.c_float,
+                                   ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_int64),
+                                   ctypes.POINTER(ctypes.c_int64)]),
+    'ffn_evaluation_read_seed': (_I, [_P, _I, _P]),
+    'ffn_evaluation_read_labels': (_I, [_P, _I, _P]),
+    'ffn_evaluation_read_image': (_I, [_P, _I, _P]),
+    'ffn_evaluation_write_seed': (_I, [_P, _I, _P]),
+    'ffn_evaluation_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

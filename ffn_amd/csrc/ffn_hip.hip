@@ -2069,6 +2069,50 @@ int ffn_predict(ffn_engine* e, int n, const float* seed, const float* image,
   return FFN_OK;
 }
 
+int ffn_predict_device(ffn_engine* e, int n, const float* seed_dev,
+                       const float* image_dev, float* logits_dev) {
+  EngineLock lock_(e);
+  if (!e || !seed_dev || !image_dev || !logits_dev)
+    return fail(FFN_ERR_ARG, "null argument");
+  if (n < 1 || n > e->max_batch)
+    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
+  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t bytes = (size_t)n * e->g.V * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(e->up_seed, seed_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->up_image, image_dev, bytes, hipMemcpyDeviceToDevice,
+                         e->stream));
+  StepItems si;
+  int rc = dense_items(e, n, &si);
+  if (rc) return rc;
+  rc = run_stack(e, n, si, std::nanf(""), INFINITY);
+  if (rc) return rc;
+  // The same repeats of a void run as in ffn_predict; the logits leave the engine
+  // only once a run has counted, so logits_dev may be one of the inputs.
+  for (int attempt = 0;; ++attempt) {
+    unsigned flag[2] = {0, 0};
+    if (e->conv_variant >= 6)
+      HIP_TRY(hipMemcpyAsync(flag, e->range_flag, sizeof(flag), hipMemcpyDeviceToHost,
+                             e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const bool is_void = e->conv_variant >= 6 && flag[0] == e->range_tag;
+    if (!is_void) {
+      if (e->last_stack_resident) e->flow_strikes = 0;
+      break;
+    }
+    if (attempt == 2) return fail(FFN_ERR_HIP, "ffn_predict_device: the step stayed void");
+    if (flow_voided(e, flag[1] == e->range_tag) == 0) {
+      rc = switch_variant(e, e->exact_variant);
+      if (rc) return rc;
+    }
+    rc = run_stack(e, n, si, std::nanf(""), INFINITY);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(logits_dev, e->logits, bytes, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return FFN_OK;
+}
+
 int ffn_forward_resident(ffn_engine* e, int n, int repeats) {
   EngineLock lock_(e);
   if (!e) return fail(FFN_ERR_ARG, "null argument");

@@ -287,6 +287,17 @@ class HipEngine:
       out = np.ascontiguousarray(out[self._pred_sel])
     return out
 
+  def predict_device(self, n: int, seed, image, logits):
+    """`predict` on arrays that are already on the engine's device
+    (ffn_predict_device): seed, image, logits are f32 [>= n, z, y, x] of
+    input_seed_size, given as objects with `data_ptr()` (torch tensors) or as
+    addresses; whatever wrote the inputs has completed.  The logits cover the
+    whole FoV (the centred pred_mask box of it is what `predict` returns);
+    `logits` may be one of the inputs."""
+    ptr = lambda a: int(a.data_ptr()) if hasattr(a, 'data_ptr') else int(a)
+    check(self._lib.ffn_predict_device(self._h, int(n), ptr(seed), ptr(image),
+                                       ptr(logits)))
+
   def forward_resident(self, n: int = 1, repeats: int = 1):
     check(self._lib.ffn_forward_resident(self._h, n, repeats))
 

@@ -19,12 +19,9 @@ def noise_volume(shape=(250, 250, 250), seed=0) -> np.ndarray:
   return np.random.RandomState(seed).randint(0, 256, shape).astype(np.uint8)
 
 
-def cells_volume(shape=(250, 250, 250), seed=1234, cells_per_96cube=12.0,
-                 membrane=60.0, interior=160.0, noise_sigma=10.0,
-                 membrane_dilate=1, blur_sigma=1.0) -> np.ndarray:
-  """Voronoi-membrane phantom, uint8 zyx."""
-  rng = np.random.RandomState(seed)
-  shape = tuple(int(s) for s in shape)
+def _voronoi(shape, rng, cells_per_96cube, membrane_dilate):
+  """(nearest-centre labels int32, membrane mask) of the phantom; draws the
+  cell centres from `rng`."""
   n_cells = max(2, int(round(cells_per_96cube * np.prod(shape) / 96.0**3)))
   centers = rng.uniform(0, 1, (n_cells, 3)) * np.array(shape)[None]
   # Nearest-centre labelling in z-slabs to bound memory.
@@ -49,11 +46,31 @@ def cells_volume(shape=(250, 250, 250), seed=1234, cells_per_96cube=12.0,
     edge[tuple(sl_hi)] |= d
   if membrane_dilate > 0:
     edge = ndimage.binary_dilation(edge, iterations=membrane_dilate)
+  return labels, edge
+
+
+def cells_volume(shape=(250, 250, 250), seed=1234, cells_per_96cube=12.0,
+                 membrane=60.0, interior=160.0, noise_sigma=10.0,
+                 membrane_dilate=1, blur_sigma=1.0) -> np.ndarray:
+  """Voronoi-membrane phantom, uint8 zyx."""
+  rng = np.random.RandomState(seed)
+  shape = tuple(int(s) for s in shape)
+  _, edge = _voronoi(shape, rng, cells_per_96cube, membrane_dilate)
   vol = np.where(edge, membrane, interior).astype(np.float32)
   vol += rng.normal(0, noise_sigma, shape).astype(np.float32)
   if blur_sigma > 0:
     vol = ndimage.gaussian_filter(vol, blur_sigma)
   return np.clip(np.rint(vol), 0, 255).astype(np.uint8)
+
+
+def cells_labels(shape=(250, 250, 250), seed=1234, cells_per_96cube=12.0,
+                 membrane_dilate=1) -> np.ndarray:
+  """Ground-truth segmentation of `cells_volume` with the same parameters:
+  uint64 zyx, cell k as id k + 1 and the membranes as background (0)."""
+  shape = tuple(int(s) for s in shape)
+  labels, edge = _voronoi(shape, np.random.RandomState(seed), cells_per_96cube,
+                          membrane_dilate)
+  return np.where(edge, 0, labels.astype(np.int64) + 1).astype(np.uint64)
 
 
 def shared_volume(build, path, rank=0, barrier=None):

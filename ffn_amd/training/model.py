@@ -1,7 +1,8 @@
 """Geometry of an FFN model (host-side mirror of reference ffn/training/model.py).
 
-Only what the inference path needs: `ModelInfo` (reference model.py:25-46) and
-a minimal `FFNModel` base carrying it (reference model.py:64-113).  There is no
+Only what the inference path and the forward-only evaluation need: `ModelInfo`
+(reference model.py:25-46) and a minimal `FFNModel` base carrying it and the
+`shifts` of the fixed move policy (reference model.py:64-113).  There is no
 graph: the forward pass lives in csrc/ as HIP kernels.
 """
 
@@ -34,6 +35,18 @@ class FFNModel:
     for name in ('deltas', 'pred_mask_size', 'input_seed_size',
                  'input_image_size'):
       setattr(self.info, name, np.array(getattr(self.info, name)))
+    # The moves of the fixed step size policy, (x, y, z), in the reference's
+    # order (reference model.py:75-81).  A model made without a geometry has
+    # none: ConvStack3DFFNModel's fov_size and deltas default to None.
+    self.shifts = []
+    if self.info.deltas.shape == (3,):
+      d = [int(v) for v in self.info.deltas]
+      for dx in (-d[0], 0, d[0]):
+        for dy in (-d[1], 0, d[1]):
+          for dz in (-d[2], 0, d[2]):
+            if dx == 0 and dy == 0 and dz == 0:
+              continue
+            self.shifts.append((dx, dy, dz))
 
   def update_seed(self, seed, update):
     """Updates the initial `seed` with `update` (reference model.py:168-183).

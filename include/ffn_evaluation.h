@@ -1,0 +1,175 @@
+/*
+ * libffn_hip.so, forward-only evaluation on training examples -- the FoV loop
+ * of the google/ffn checkout's train.py (train.py:202-286 example loading,
+ * ffn/training/examples.py and mask.py for seed, crops, moves and the seed
+ * update, ffn/training/tracker.py EvalTracker.add_patch for the metrics), run
+ * without an optimiser.  This unit owns the data and the voxel work of that
+ * loop; it knows nothing about the engine.  A driver composes it with
+ * ffn_predict_device (ffn_hip.h): gather -> ffn_predict_device -> paste.
+ *
+ * Conventions as in ffn_coordinates.h: plain C types, 0 / negative FFN_ERR_*
+ * return codes, ffn_last_error() for the message, (z, y, x) order unless a
+ * name says xyz, the caller owns host buffers.  A handle owns one HIP stream
+ * and device storage; calls on one handle must be serialised.  Every call
+ * returns with its kernels complete.  Pointers named *_dev are device memory
+ * of the handle's device; whatever wrote them has completed before the call.
+ *
+ * Exact definition.  With the geometry of ffn_evaluation_configure, a slot
+ * holds three dense f32 arrays: the seed canvas (canvas_zyx), the image patch
+ * (image_patch_zyx) and the label patch (label_patch_zyx).  For a size s the
+ * centre index is s / 2 (integer division) and a patch of size s centred on
+ * voxel c of a volume starts at c - (s - 1) / 2 (inputs.py:339-345).
+ *
+ * load.  image[p] = ((float)v - offset) / scale in f32, the subtraction first,
+ * both IEEE-rounded (inputs.py:437); v is the volume's u8 or f32 voxel.
+ * labels[p] = (l > 0 && l == l_centre) ? 0.95f : 0.05f with l the volume's
+ * label at p and l_centre the one at the label patch's centre index, compared
+ * as unsigned 64-bit values (4-byte labels are zero-extended).  seed[p] =
+ * seed_pad_logit everywhere, seed_centre_logit at the canvas centre index.
+ *
+ * An offset (x, y, z) addresses, for an array of size S and a crop of size C,
+ * the box that starts at S / 2 - C / 2 + offset per axis (mask.crop_and_pad).
+ * gather copies that box of the seed canvas (C = input_seed) and of the image
+ * patch (C = input_image).  paste overwrites, inside the input_seed box at the
+ * offset, the centred pred_mask box (it starts (input_seed - pred_mask) / 2
+ * into it; examples.py:143-156) with the logits.  probe_moves reads
+ * seed[canvas / 2 + offset] >= seed_threshold and labels[label_patch / 2 +
+ * offset] >= label_threshold (examples._eval_move).  score_faces takes the
+ * pred_mask box of the seed canvas at the offset and, with c = pred_mask / 2
+ * and d = deltas, the working box [c - d, c + d] per axis; face f = 2 * axis +
+ * (0 for -d, 1 for +d), axes in z, y, x order, is that box with `axis` fixed at
+ * c -/+ d.  Its score is the largest value of the face and its position the
+ * first one holding it in C order (np.argmax; the seed holds no NaN), given
+ * relative to the box centre: (dz, dy, dx) with the fixed axis at -/+ d
+ * (movement.get_scored_move_offsets, which then drops scores below its
+ * threshold and axes of delta 0: that is left to the caller).
+ *
+ * finish.  Over the eval_zyx boxes at offset 0 of the seed canvas (x) and the
+ * label patch (z): loss_sum = sum of max(x, 0) - x * z + log1p(exp(-|x|)), the
+ * numerically stable form TensorFlow documents for
+ * sigmoid_cross_entropy_with_logits, with weight 1, in f32: every thread sums
+ * its voxels in index order, then lanes, waves and workgroups are combined as
+ * a fixed tree, so the sum is the same from run to run.  counts (tp, tn, fp,
+ * fn) with pred = x >= pred_threshold and true = z > 0.5f are exact.  The loss
+ * weights of an unaugmented example are all 1, so no voxel is masked and
+ * *masked is 0.
+ */
+#ifndef FFN_EVALUATION_H_
+#define FFN_EVALUATION_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "ffn_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FFN_EVALUATION_MAX_SLOTS 32
+/* ffn_evaluation_paste: how logits_dev is laid out. */
+#define FFN_EVALUATION_LOGITS_PRED 0 /* dense [n][pred_mask]                  */
+#define FFN_EVALUATION_LOGITS_FOV 1  /* dense [n][input_seed], what
+                                        ffn_predict_device writes; the centred
+                                        pred_mask box of it is read           */
+
+typedef struct ffn_evaluation ffn_evaluation;
+
+typedef struct ffn_evaluation_geometry {
+  int32_t input_seed_zyx[3];
+  int32_t input_image_zyx[3];
+  int32_t pred_mask_zyx[3];
+  int32_t deltas_zyx[3];
+  int32_t canvas_zyx[3];      /* train.py:177-179 */
+  int32_t image_patch_zyx[3]; /* train.py:172-174 */
+  int32_t label_patch_zyx[3]; /* train.py:162-164 */
+  int32_t eval_zyx[3];        /* train.py:167-169 */
+  int32_t slots;              /* 1 .. FFN_EVALUATION_MAX_SLOTS */
+} ffn_evaluation_geometry;
+
+int ffn_evaluation_create(int device_id, ffn_evaluation** out);
+void ffn_evaluation_destroy(ffn_evaluation* h);
+
+/* Sets the geometry and allocates the slots (their contents are undefined
+ * until loaded).  Every size is positive; per axis pred_mask <= input_seed with
+ * an even difference, input_seed <= canvas, input_image <= image_patch,
+ * pred_mask <= label_patch, and eval <= canvas and <= label_patch.  Volumes
+ * are kept. */
+int ffn_evaluation_configure(ffn_evaluation* h,
+                             const ffn_evaluation_geometry* geometry);
+
+/* Three device arrays owned by the handle, valid until the next configure or
+ * destroy, for a driver that has no allocator of its own: seed [slots]
+ * [input_seed], image [slots][input_image] (the outputs of gather) and logits
+ * [slots][input_seed] (what ffn_predict_device writes and paste reads). */
+int ffn_evaluation_io_buffers(ffn_evaluation* h, float** seed_dev,
+                              float** image_dev, float** logits_dev);
+
+/* Forgets every volume. */
+int ffn_evaluation_reset(ffn_evaluation* h);
+
+/* Copies a HOST image (image_elem 1 = uint8, 4 = f32) and HOST labels
+ * (label_elem 4 or 8 bytes, unsigned) of one shape to the device, where they
+ * stay; *index is the volume's number. */
+int ffn_evaluation_add_volume(ffn_evaluation* h, const void* image,
+                              int image_elem, const void* labels,
+                              int label_elem, const int64_t shape_zyx[3],
+                              int32_t* index);
+
+/* Fills slots[k] from volumes[k] around centres_xyz[3 k ..] for k < n, in one
+ * launch (n <= slots, the slots distinct).  If any patch leaves its volume the
+ * call is FFN_ERR_ARG and no slot is touched. */
+int ffn_evaluation_load(ffn_evaluation* h, int n, const int32_t* slots,
+                        const int32_t* volumes, const int32_t* centres_xyz,
+                        const float* offsets, const float* scales,
+                        float seed_pad_logit, float seed_centre_logit);
+
+/* n (slot, offset) pairs, any number, in one launch -> valid[k], wanted[k]
+ * (0 / 1).  An offset outside the canvas or the label patch is FFN_ERR_ARG. */
+int ffn_evaluation_probe_moves(ffn_evaluation* h, size_t n,
+                               const int32_t* slots, const int32_t* offsets_xyz,
+                               float seed_threshold, float label_threshold,
+                               uint8_t* valid, uint8_t* wanted);
+
+/* seed_out_dev: [n][input_seed], image_out_dev: [n][input_image], f32, entry k
+ * from slots[k] at offsets_xyz[3 k ..]; n <= slots.  A box that leaves the
+ * canvas or the image patch is FFN_ERR_ARG; nothing is written then. */
+int ffn_evaluation_gather(ffn_evaluation* h, int n, const int32_t* slots,
+                          const int32_t* offsets_xyz, float* seed_out_dev,
+                          float* image_out_dev);
+
+/* The seed update; the slots distinct, n <= slots. */
+int ffn_evaluation_paste(ffn_evaluation* h, int n, const int32_t* slots,
+                         const int32_t* offsets_xyz, const float* logits_dev,
+                         int logits_layout);
+
+/* scores: 6 per entry; positions_zyx: 6 x 3 per entry.  deltas <= pred_mask / 2
+ * per axis, else FFN_ERR_ARG. */
+int ffn_evaluation_score_faces(ffn_evaluation* h, int n, const int32_t* slots,
+                               const int32_t* offsets_xyz, float* scores,
+                               int32_t* positions_zyx);
+
+/* counts: tp, tn, fp, fn. */
+int ffn_evaluation_finish(ffn_evaluation* h, int slot, float pred_threshold,
+                          float* loss_sum, int64_t counts[4], int64_t* masked);
+
+/* Whole arrays of a slot to / from the host (canvas, label patch, image patch
+ * sizes).  write_seed replaces the seed canvas. */
+int ffn_evaluation_read_seed(ffn_evaluation* h, int slot, float* out);
+int ffn_evaluation_read_labels(ffn_evaluation* h, int slot, float* out);
+int ffn_evaluation_read_image(ffn_evaluation* h, int slot, float* out);
+int ffn_evaluation_write_seed(ffn_evaluation* h, int slot, const float* in);
+
+/* HIP-event kernel time (no host<->device copies) of the last load (index 0),
+ * probe_moves (1), gather (2), paste (3), score_faces (4) and finish (5) on
+ * this handle, and the bytes each is specified to move (algorithmic: load, the
+ * volume voxels read and the three arrays written; probe, 8 bytes read per
+ * pair; gather and paste, every f32 once in and once out; score_faces, the six
+ * faces; finish, the two eval boxes). */
+int ffn_evaluation_last_timing(ffn_evaluation* h, double kernel_ms[6],
+                               double algorithmic_bytes[6]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FFN_EVALUATION_H_ */

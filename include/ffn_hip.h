@@ -151,6 +151,13 @@ size_t ffn_engine_weight_count(int depth, int features);
  * seed, image, logits_out: host arrays [n][fz][fy][fx] f32, n <= max_batch.   */
 int ffn_predict(ffn_engine* engine, int n, const float* seed,
                 const float* image, float* logits_out);
+/* The same step on DEVICE arrays of the engine's device (same layout, same
+ * kernels, same bits): for a caller whose FoVs are already resident, e.g. the
+ * training-example loop of ffn_evaluation.h.  Whatever wrote seed_dev and
+ * image_dev has completed before the call; the call returns with logits_dev
+ * written.  logits_dev may be seed_dev or image_dev.                          */
+int ffn_predict_device(ffn_engine* engine, int n, const float* seed_dev,
+                       const float* image_dev, float* logits_dev);
 
 /* Conv stack only, on whatever FoVs are resident in the engine's staging
  * buffers (no host traffic) -- the kernel-only leg of bench.py. */
