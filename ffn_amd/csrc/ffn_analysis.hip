@@ -45,8 +45,10 @@ using ffn_table::u32;
 using ffn_table::u64;
 using ffn_table::kBackground;
 using ffn_table::kEmptyKey;
-using ffn_table::mix64;
+using ffn_table::block_claim;
 using ffn_table::run_leaders;
+using ffn_table::run_mask;
+using ffn_table::table_grow;
 using ffn_table::table_insert;
 
 constexpr int kThreads = 256;
@@ -56,7 +58,6 @@ constexpr int kGroupsPerBlock = 64;          // mask pass: 64 x 64 voxels
 constexpr size_t kLineLdsBytes = 48 * 1024;  // tile of a y / z pass
 constexpr int kEndIters = 32;                // endpoint pass: 32 x 256 voxels
 constexpr int kLdsSlots = 1024;              // per-block id table
-constexpr int kLdsProbes = 16;
 constexpr size_t kGroupBytes = (size_t)1 << 30;  // device bytes of one group
 constexpr int kMaxGroupPoints = 4096;
 
@@ -338,27 +339,16 @@ __global__ __launch_bounds__(kThreads) void endpoint_count_kernel(
     const u64 leaders = run_leaders(key, valid, lane);
     made += __popcll(nm);
     if ((leaders >> lane) & 1) {
-      // the run of this leader: up to the next leader or the end of the wave
-      const u64 above = lane == 63 ? 0ull : leaders & (~0ull << (lane + 1));
-      const u64 below_end =
-          above ? ((1ull << __builtin_ctzll(above)) - 1) : ~0ull;
-      const u64 run = below_end & (~0ull << lane);
+      const u64 run = run_mask(leaders, lane);
       const u32 cnt = __popcll(vm & run), ov = __popcll(nm & run);
       if (key == kEmptyKey) {
         flags[1] = 1;
       } else {
-        u32 s = mix64(key) & (kLdsSlots - 1);
-        bool done = false;
-        for (int probe = 0; probe < kLdsProbes && !done; ++probe) {
-          const u64 prev = atomicCAS(&skeys[s], kEmptyKey, key);
-          if (prev == kEmptyKey || prev == key) {
-            atomicAdd(&sorig[s], cnt);
-            if (ov) atomicAdd(&sover[s], ov);
-            done = true;
-          }
-          s = (s + 1) & (kLdsSlots - 1);
-        }
-        if (!done) {  // block table crowded: straight to the global one
+        const int s = block_claim<kLdsSlots>(skeys, key);
+        if (s >= 0) {
+          atomicAdd(&sorig[s], cnt);
+          if (ov) atomicAdd(&sover[s], ov);
+        } else {  // block table crowded: straight to the global one
           const u32 t = table_insert(gkeys, mask, key, flags);
           if (t != kBackground) {
             atomicAdd(&gvals[2 * (size_t)t + 1], cnt);
@@ -734,14 +724,17 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
     starts[count] = (int)blocks;
     uint8_t* dev = static_cast<uint8_t*>(a->in.p);
     U_TRY(hipMemcpyAsync(dev, stage, upload, hipMemcpyHostToDevice, s));
-    for (;;) {
-      const size_t slots = (size_t)a->nslots * count;
-      U_OK(ensure(a->keys, slots * 8));
+    // growth stops at 2^26 slots per point or 8 GiB (64 bytes per slot, the
+    // table that would follow counted) for the group
+    const u32 limit =
+        (u32)std::min<size_t>((size_t)1 << 26, ((size_t)1 << 27) / count + 1);
+    int state[2];
+    U_OK(table_grow(s, a->keys, count, &a->nslots, limit, flags, state,
+                    [&](u32 mask) {
+      const size_t slots = ((size_t)mask + 1) * count;
       U_OK(ensure(a->vals, slots * 8));
-      U_TRY(hipMemsetAsync(a->keys.p, 0xff, slots * 8, s));
       U_TRY(hipMemsetAsync(a->vals.p, 0, slots * 8, s));
       U_TRY(hipMemsetAsync(a->small.p, 0, count * 8, s));
-      U_TRY(hipMemsetAsync(flags, 0, 8, s));
       U_OK(a->timer_start());
       hipLaunchKernelGGL(
           endpoint_count_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s,
@@ -749,19 +742,12 @@ int ffn_analyzer_endpoint_overlaps(ffn_analyzer* a,
           reinterpret_cast<const int*>(dev + starts_off), (int)count,
           (const uint8_t*)dev, (const uint8_t*)dev,
           static_cast<u64*>(a->keys.p), static_cast<u32*>(a->vals.p),
-          a->nslots - 1, flags, static_cast<u64*>(a->small.p));
+          mask, flags, static_cast<u64*>(a->small.p));
       U_TRY(hipGetLastError());
-      U_OK(add_elapsed(a, &a->ms[1]));
-      int host_flags[2] = {0, 0};
-      U_TRY(hipMemcpy(host_flags, flags, 8, hipMemcpyDeviceToHost));
-      if (host_flags[1])
-        return ffn_set_error(FFN_ERR_ARG, "segment id 2^64 - 1 is not supported");
-      if (!host_flags[0]) break;
-      if (a->nslots >= (1u << 26) || slots * 4 * 16 > ((size_t)8 << 30))
-        return ffn_set_error(FFN_ERR_ARG, "id table overflow at %u slots",
-                             a->nslots);
-      a->nslots <<= 2;
-    }
+      return add_elapsed(a, &a->ms[1]);
+    }));
+    if (state[1])
+      return ffn_set_error(FFN_ERR_ARG, "segment id 2^64 - 1 is not supported");
     const long long total = (long long)a->nslots * (long long)count;
     U_OK(a->timer_start());
     hipLaunchKernelGGL(endpoint_emit_kernel,

@@ -35,8 +35,9 @@ using ffn_table::u32;
 using ffn_table::u64;
 using ffn_table::kBackground;
 using ffn_table::kEmptyKey;
-using ffn_table::mix64;
+using ffn_table::block_claim;
 using ffn_table::table_find;
+using ffn_table::table_grow;
 using ffn_table::table_insert;
 
 constexpr int kThreads = 256;
@@ -44,7 +45,6 @@ constexpr int kMaxAxis = 4096;
 constexpr size_t kLineLdsBytes = 48 * 1024;  // tile of a y / z pass
 constexpr int kLineBytesPerVoxel = 12;       // f64 d2 + u32 id
 constexpr int kLdsSlots = 1024;              // per-block pair table
-constexpr int kLdsProbes = 16;
 
 // Label of a voxel as the kernels see it: 0 = unlabelled.  Sets *bad for an id
 // that does not fit the 32-bit state.
@@ -276,18 +276,10 @@ __global__ __launch_bounds__(kThreads) void contact_min_kernel(
       double dist;
       if (!contact(id, edt, g, i, z, y, x, a, ea, o, &key, &dist)) continue;
       const u64 bits = dist_bits(dist);
-      u32 s = mix64(key) & (kLdsSlots - 1);
-      bool done = false;
-      for (int probe = 0; probe < kLdsProbes; ++probe) {
-        const u64 prev = atomicCAS(&skeys[s], kEmptyKey, key);
-        if (prev == kEmptyKey || prev == key) {
-          atomicMin(&svals[s], bits);
-          done = true;
-          break;
-        }
-        s = (s + 1) & (kLdsSlots - 1);
-      }
-      if (!done) {  // block table crowded: straight to the global one
+      const int s = block_claim<kLdsSlots>(skeys, key);
+      if (s >= 0) {
+        atomicMin(&svals[s], bits);
+      } else {  // block table crowded: straight to the global one
         const u32 t = table_insert(keys, mask, key, overflow);
         if (t != kBackground) atomicMin(&vals[t], bits);
       }
@@ -565,29 +557,23 @@ int ffn_decision_contact_minima(ffn_decision* h, const int64_t lo_zyx[3],
   U_OK(ensure(h->small, 64));
   int* overflow = static_cast<int*>(h->small.p);
   u64* n_out = reinterpret_cast<u64*>(h->small.p) + 1;
+  U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+  int state[2];  // (word 1 is not used: the expansion has refused bad ids)
   u32 nslots = std::max<u32>(h->nslots, 1u << 18);
   double ms = 0.0;
-  for (;;) {
-    U_OK(ensure(h->keys, (size_t)nslots * 8));
-    U_OK(ensure(h->vals, (size_t)nslots * 8));
-    U_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
-    U_TRY(hipMemsetAsync(h->vals.p, 0xff, (size_t)nslots * 8, h->stream));
-    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+  U_OK(table_grow(h->stream, h->keys, 1, &nslots, 1u << 28, overflow, state,
+                  [&](u32 mask) {
+    U_OK(ensure(h->vals, ((size_t)mask + 1) * 8));
+    U_TRY(hipMemsetAsync(h->vals.p, 0xff, ((size_t)mask + 1) * 8, h->stream));
     U_OK(h->timer_start());
     const int blocks = (int)std::min<long long>(
         2048, std::max<long long>(1, (g.n + 16 * kThreads - 1) / (16 * kThreads)));
     hipLaunchKernelGGL(contact_min_kernel, dim3(blocks), dim3(kThreads), 0,
                        h->stream, id, edt, g, static_cast<u64*>(h->keys.p),
-                       static_cast<u64*>(h->vals.p), nslots - 1, overflow);
+                       static_cast<u64*>(h->vals.p), mask, overflow);
     U_TRY(hipGetLastError());
-    U_OK(h->timer_stop(&ms));
-    int ov = 0;
-    U_TRY(hipMemcpy(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost));
-    if (!ov) break;
-    if (nslots >= (1u << 28))
-      return ffn_set_error(FFN_ERR_ARG, "pair table overflow at 2^28 slots");
-    nslots <<= 2;
-  }
+    return h->timer_stop(&ms);
+  }));
   h->nslots = nslots;
   U_OK(ensure(h->out_key, cap * 8));
   U_OK(ensure(h->out_dist, cap * 8));

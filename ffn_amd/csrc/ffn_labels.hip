@@ -23,14 +23,16 @@ using ffn_table::u32;
 using ffn_table::u64;
 using ffn_table::kBackground;
 using ffn_table::kEmptyKey;
-using ffn_table::mix64;
+using ffn_table::block_claim;
 using ffn_table::run_leaders;
+using ffn_table::run_mask;
+using ffn_table::table_compact_kernel;
 using ffn_table::table_find;
+using ffn_table::table_grow;
 using ffn_table::table_insert;
 
 constexpr int kThreads = 256;
 constexpr int kLdsSlots = 2048;      // per-block pre-aggregation table
-constexpr int kLdsProbes = 16;
 constexpr int kScanTile = 2048;       // elements per block in the root ranking
 
 template <typename T>
@@ -65,23 +67,13 @@ __global__ __launch_bounds__(kThreads) void pair_count_kernel(
                   (sizeof(T) == 8 && b && (((u64)a[i] | (u64)b[i]) >> 32))))
       *overflow = 2;  // id outside the packable range (caller must remap)
     const u64 leaders = run_leaders(key, valid, lane);
-    const int nvalid = __popcll(__ballot(valid));
+    const u64 vm = __ballot(valid);
     if (valid && ((leaders >> lane) & 1)) {
-      const u64 above = lane == 63 ? 0 : leaders & ~((2ull << lane) - 1);
-      const int end = above ? __ffsll((long long)above) - 1 : nvalid;
-      const u32 run = (u32)(end - lane);
-      u32 s = mix64(key) & (kLdsSlots - 1);
-      bool done = false;
-      for (int probe = 0; probe < kLdsProbes; ++probe) {
-        const u64 prev = atomicCAS(&skeys[s], kEmptyKey, key);
-        if (prev == kEmptyKey || prev == key) {
-          atomicAdd(&scnt[s], run);
-          done = true;
-          break;
-        }
-        s = (s + 1) & (kLdsSlots - 1);
-      }
-      if (!done) {  // block table crowded: straight to the global one
+      const u32 run = (u32)__popcll(vm & run_mask(leaders, lane));
+      const int s = block_claim<kLdsSlots>(skeys, key);
+      if (s >= 0) {
+        atomicAdd(&scnt[s], run);
+      } else {  // block table crowded: straight to the global one
         const u32 g = table_insert(keys, mask, key, overflow);
         if (g != kBackground) atomicAdd(&counts[g], (u64)run);
       }
@@ -94,21 +86,6 @@ __global__ __launch_bounds__(kThreads) void pair_count_kernel(
       const u32 g = table_insert(keys, mask, skeys[s], overflow);
       if (g != kBackground) atomicAdd(&counts[g], (u64)c);
     }
-  }
-}
-
-__global__ void table_compact_kernel(const u64* keys, const u64* counts,
-                                     u32 nslots, u64* out_key, u64* out_count,
-                                     u32* out_slot, u32 cap, u32* n_out) {
-  const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nslots) return;
-  const u64 k = keys[s];
-  if (k == kEmptyKey) return;
-  const u32 j = atomicAdd(n_out, 1u);
-  if (j < cap) {
-    out_key[j] = k;
-    out_count[j] = counts[s];
-    out_slot[j] = s;
   }
 }
 
@@ -359,12 +336,9 @@ __global__ __launch_bounds__(kThreads) void cc_output_kernel(
   if (sizes) {
     // one atomic per run of equal ids in the wave
     const u64 leaders = run_leaders((u64)id, valid, lane);
-    const int nvalid = __popcll(__ballot(valid));
-    if (valid && id != 0 && ((leaders >> lane) & 1)) {
-      const u64 above = lane == 63 ? 0 : leaders & ~((2ull << lane) - 1);
-      const int end = above ? __ffsll((long long)above) - 1 : nvalid;
-      if (id - 1 < cap) atomicAdd(&sizes[id - 1], (u64)(end - lane));
-    }
+    const u64 vm = __ballot(valid);
+    if (valid && id != 0 && ((leaders >> lane) & 1) && id - 1 < cap)
+      atomicAdd(&sizes[id - 1], (u64)__popcll(vm & run_mask(leaders, lane)));
   }
 }
 
@@ -464,13 +438,37 @@ u32 table_size_for(size_t expected) {
   return s;
 }
 
-int alloc_table(ffn_labels* h, u32 nslots, bool with_counts) {
-  U_OK(ensure(h->keys, (size_t)nslots * 8));
+// The payload of a table of `nslots` keys: a label per slot and, for
+// pair_counts, a count (zeroed).
+int alloc_payload(ffn_labels* h, u32 nslots, bool with_counts) {
   U_OK(ensure(h->slot_label, (size_t)nslots * 8));
-  if (with_counts) U_OK(ensure(h->counts, (size_t)nslots * 8));
-  U_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
-  if (with_counts)
-    U_TRY(hipMemsetAsync(h->counts.p, 0, (size_t)nslots * 8, h->stream));
+  if (!with_counts) return FFN_OK;
+  U_OK(ensure(h->counts, (size_t)nslots * 8));
+  U_TRY(hipMemsetAsync(h->counts.p, 0, (size_t)nslots * 8, h->stream));
+  return FFN_OK;
+}
+
+// Table of the remap calls: key -> value in slot_label; the keys and values are
+// in aux0 / aux1 already.
+int build_map(ffn_labels* h, size_t n_keys) {
+  U_OK(ensure(h->small, 64));
+  int state[2];
+  u32 nslots = table_size_for(n_keys);
+  U_OK(table_grow(h->stream, h->keys, 1, &nslots, 1u << 30,
+                  static_cast<int*>(h->small.p), state, [&](u32 mask) {
+    U_OK(alloc_payload(h, mask + 1, false));
+    if (n_keys)
+      hipLaunchKernelGGL(map_build_kernel, dim3((n_keys + 255) / 256),
+                         dim3(256), 0, h->stream,
+                         static_cast<const u64*>(h->aux0.p),
+                         static_cast<const u64*>(h->aux1.p), (u32)n_keys,
+                         static_cast<u64*>(h->keys.p),
+                         static_cast<u64*>(h->slot_label.p), mask,
+                         static_cast<int*>(h->small.p));
+    U_TRY(hipGetLastError());
+    return (int)FFN_OK;
+  }));
+  h->nslots = nslots;
   return FFN_OK;
 }
 
@@ -481,39 +479,33 @@ int pair_counts_impl(ffn_labels* h, size_t n, size_t cap, uint64_t* pair_a,
   const T* a = static_cast<const T*>(h->a.p);
   const T* b = h->have_b ? static_cast<const T*>(h->b.p) : nullptr;
   U_OK(ensure(h->small, 64));
+  U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
   int* overflow = static_cast<int*>(h->small.p);
-  u32* n_out = reinterpret_cast<u32*>(h->small.p) + 1;
+  u32* n_out = reinterpret_cast<u32*>(h->small.p) + 2;
+  int state[2];
   u32 nslots = std::max<u32>(h->nslots, 1u << 20);
-  for (;;) {
-    U_OK(alloc_table(h, nslots, true));
-    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+  U_OK(table_grow(h->stream, h->keys, 1, &nslots, 1u << 30, overflow, state,
+                  [&](u32 mask) {
+    U_OK(alloc_payload(h, mask + 1, true));
     U_OK(h->timer_start());
     const int blocks = (int)std::min<size_t>(
         2048, std::max<size_t>(1, (n + 16 * kThreads - 1) / (16 * kThreads)));
     hipLaunchKernelGGL((pair_count_kernel<T>), dim3(blocks), dim3(kThreads), 0,
                        h->stream, a, b, n, static_cast<u64*>(h->keys.p),
-                       static_cast<u64*>(h->counts.p), nslots - 1, overflow);
+                       static_cast<u64*>(h->counts.p), mask, overflow);
     U_TRY(hipGetLastError());
-    U_OK(stop_timer(h, (double)n * sizeof(T) * (b ? 2 : 1)));
-    int ov = 0;
-    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
-                         h->stream));
-    U_TRY(hipStreamSynchronize(h->stream));
-    if (!ov) break;
-    if (ov == 2)
-      return ffn_set_error(FFN_ERR_ARG,
-                           "label id >= 2^32 - 1: remap ids before pairing");
-    if (nslots >= (1u << 30))
-      return ffn_set_error(FFN_ERR_ARG, "pair table overflow at 2^30 slots");
-    nslots <<= 2;
-  }
+    return stop_timer(h, (double)n * sizeof(T) * (b ? 2 : 1));
+  }));
+  if (state[0])  // (2: an id outside the packable range)
+    return ffn_set_error(FFN_ERR_ARG,
+                         "label id >= 2^32 - 1: remap ids before pairing");
   h->nslots = nslots;
   // compact the occupied slots into dense arrays (order unspecified)
   const size_t want = std::min<size_t>(cap, nslots);
   U_OK(ensure(h->aux0, want * 8));
   U_OK(ensure(h->aux1, want * 8));
   U_OK(ensure(h->aux2, want * 4));
-  hipLaunchKernelGGL(table_compact_kernel, dim3((nslots + 255) / 256),
+  hipLaunchKernelGGL(table_compact_kernel<u64>, dim3((nslots + 255) / 256),
                      dim3(256), 0, h->stream,
                      static_cast<const u64*>(h->keys.p),
                      static_cast<const u64*>(h->counts.p), nslots,
@@ -624,10 +616,13 @@ int ffn_labels_pair_counts(ffn_labels* h, const void* a, const void* b,
   h->n = n;
   h->elem_bytes = elem_bytes;
   h->have_b = b != nullptr;
-  if (n == 0) {
+  if (n == 0) {  // an empty table, so that apply_pair_labels finds one
+    U_OK(ensure(h->small, 64));
+    int state[2];
     h->nslots = std::max<u32>(h->nslots, 1u << 20);
-    U_OK(alloc_table(h, h->nslots, true));
-    U_TRY(hipStreamSynchronize(h->stream));
+    U_OK(table_grow(h->stream, h->keys, 1, &h->nslots, 1u << 30,
+                    static_cast<int*>(h->small.p), state,
+                    [&](u32 mask) { return alloc_payload(h, mask + 1, true); }));
     h->pairs_valid = true;
     h->last_ms = 0.0;
     h->last_bytes = 0.0;
@@ -702,37 +697,13 @@ int ffn_labels_remap(ffn_labels* h, const void* in, int elem_bytes, size_t n,
   U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   if (n == 0) return FFN_OK;
-  U_OK(ensure(h->small, 64));
-  int* overflow = static_cast<int*>(h->small.p);
-  u32 nslots = table_size_for(n_keys);
   U_OK(ensure(h->aux0, std::max<size_t>(n_keys, 1) * 8));
   U_OK(ensure(h->aux1, std::max<size_t>(n_keys, 1) * 8));
   U_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
   U_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
-  for (;;) {
-    U_OK(alloc_table(h, nslots, false));
-    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
-    if (n_keys)
-      hipLaunchKernelGGL(map_build_kernel, dim3((n_keys + 255) / 256),
-                         dim3(256), 0, h->stream,
-                         static_cast<const u64*>(h->aux0.p),
-                         static_cast<const u64*>(h->aux1.p), (u32)n_keys,
-                         static_cast<u64*>(h->keys.p),
-                         static_cast<u64*>(h->slot_label.p), nslots - 1,
-                         overflow);
-    U_TRY(hipGetLastError());
-    int ov = 0;
-    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
-                         h->stream));
-    U_TRY(hipStreamSynchronize(h->stream));
-    if (!ov) break;
-    if (nslots >= (1u << 30))
-      return ffn_set_error(FFN_ERR_ARG, "remap table overflow");
-    nslots <<= 2;
-  }
-  h->nslots = nslots;
+  U_OK(build_map(h, n_keys));
   h->n = n;
   h->elem_bytes = elem_bytes;
   h->have_b = false;
@@ -943,34 +914,13 @@ int ffn_labels_remap_device(ffn_labels* h, int32_t* vol_dev, size_t n,
   U_TRY(hipSetDevice(h->device_id));
   h->pairs_valid = false;
   if (n == 0 || n_keys == 0) return FFN_OK;
-  U_OK(ensure(h->small, 64));
-  int* overflow = static_cast<int*>(h->small.p);
-  u32 nslots = table_size_for(n_keys);
   U_OK(ensure(h->aux0, n_keys * 8));
   U_OK(ensure(h->aux1, n_keys * 8));
   U_TRY(hipMemcpyAsync(h->aux0.p, keys, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
   U_TRY(hipMemcpyAsync(h->aux1.p, values, n_keys * 8, hipMemcpyHostToDevice,
                        h->stream));
-  for (;;) {
-    U_OK(alloc_table(h, nslots, false));
-    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
-    hipLaunchKernelGGL(map_build_kernel, dim3((n_keys + 255) / 256), dim3(256), 0,
-                       h->stream, static_cast<const u64*>(h->aux0.p),
-                       static_cast<const u64*>(h->aux1.p), (u32)n_keys,
-                       static_cast<u64*>(h->keys.p),
-                       static_cast<u64*>(h->slot_label.p), nslots - 1, overflow);
-    U_TRY(hipGetLastError());
-    int ov = 0;
-    U_TRY(hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost,
-                         h->stream));
-    U_TRY(hipStreamSynchronize(h->stream));
-    if (!ov) break;
-    if (nslots >= (1u << 30))
-      return ffn_set_error(FFN_ERR_ARG, "remap table overflow");
-    nslots <<= 2;
-  }
-  h->nslots = nslots;
+  U_OK(build_map(h, n_keys));
   h->n = n;
   h->elem_bytes = 4;
   h->have_b = false;

@@ -42,7 +42,10 @@ using ffn_table::u64;
 using ffn_table::kBackground;
 using ffn_table::kEmptyKey;
 using ffn_table::run_leaders;
+using ffn_table::run_mask;
+using ffn_table::table_compact_kernel;
 using ffn_table::table_find;
+using ffn_table::table_grow;
 using ffn_table::table_insert;
 
 typedef unsigned char u8;
@@ -78,27 +81,12 @@ __global__ __launch_bounds__(kThreads) void label_count_kernel(
     const u64 key = valid ? (u64)seg[i] : kEmptyKey;
     if (valid && key == kEmptyKey) *overflow = 2;  // 2^64 - 1 marks a free slot
     const u64 leaders = run_leaders(key, valid, lane);
-    const int nvalid = __popcll(__ballot(valid));
+    const u64 vm = __ballot(valid);
     if (valid && key != kEmptyKey && ((leaders >> lane) & 1)) {
-      const u64 above = lane == 63 ? 0 : leaders & ~((2ull << lane) - 1);
-      const int end = above ? __ffsll((long long)above) - 1 : nvalid;
       const u32 s = table_insert(keys, mask, key, overflow);
-      if (s != kBackground) atomicAdd(&counts[s], (u64)(end - lane));
+      if (s != kBackground)
+        atomicAdd(&counts[s], (u64)__popcll(vm & run_mask(leaders, lane)));
     }
-  }
-}
-
-__global__ void label_compact_kernel(const u64* keys, const u64* counts,
-                                     u32 nslots, u64* out_key, u64* out_count,
-                                     u32 cap, u32* n_out) {
-  const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nslots) return;
-  const u64 k = keys[s];
-  if (k == kEmptyKey) return;
-  const u32 j = atomicAdd(n_out, 1u);
-  if (j < cap) {
-    out_key[j] = k;
-    out_count[j] = counts[s];
   }
 }
 
@@ -378,45 +366,39 @@ int label_sizes_impl(ffn_partitions* h, size_t n, size_t cap, uint64_t* ids,
                      uint64_t* sizes, size_t* n_ids) {
   const T* seg = static_cast<const T*>(h->in.p);
   U_OK(ensure(h->small, 64));
+  U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
   int* overflow = static_cast<int*>(h->small.p);
-  u32* n_out = reinterpret_cast<u32*>(h->small.p) + 1;
+  u32* n_out = reinterpret_cast<u32*>(h->small.p) + 2;
+  int state[2];
   u32 nslots = std::max<u32>(h->nslots, 1u << 18);
-  for (;;) {
-    U_OK(ensure(h->keys, (size_t)nslots * 8));
-    U_OK(ensure(h->table_counts, (size_t)nslots * 8));
-    U_TRY(hipMemsetAsync(h->keys.p, 0xff, (size_t)nslots * 8, h->stream));
-    U_TRY(hipMemsetAsync(h->table_counts.p, 0, (size_t)nslots * 8, h->stream));
-    U_TRY(hipMemsetAsync(h->small.p, 0, 64, h->stream));
+  U_OK(table_grow(h->stream, h->keys, 1, &nslots, 1u << 30, overflow, state,
+                  [&](u32 mask) {
+    U_OK(ensure(h->table_counts, ((size_t)mask + 1) * 8));
+    U_TRY(hipMemsetAsync(h->table_counts.p, 0, ((size_t)mask + 1) * 8,
+                         h->stream));
     U_OK(h->timer_start());
     const int blocks = (int)std::min<size_t>(
         2048, std::max<size_t>(1, (n + 16 * kThreads - 1) / (16 * kThreads)));
     hipLaunchKernelGGL((label_count_kernel<T>), dim3(blocks), dim3(kThreads), 0,
                        h->stream, seg, n, static_cast<u64*>(h->keys.p),
-                       static_cast<u64*>(h->table_counts.p), nslots - 1,
-                       overflow);
+                       static_cast<u64*>(h->table_counts.p), mask, overflow);
     U_TRY(hipGetLastError());
-    U_OK(h->timer_stop(&h->ms[0]));
     h->bytes[0] = (double)n * sizeof(T);
-    int ov = 0;
-    U_TRY(hipMemcpy(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost));
-    if (!ov) break;
-    if (ov == 2)
-      return ffn_set_error(FFN_ERR_ARG, "label id 2^64 - 1 is not supported");
-    if (nslots >= (1u << 30))
-      return ffn_set_error(FFN_ERR_ARG, "id table overflow at 2^30 slots");
-    nslots <<= 2;
-  }
+    return h->timer_stop(&h->ms[0]);
+  }));
+  if (state[0])  // (2: the id that marks a free slot)
+    return ffn_set_error(FFN_ERR_ARG, "label id 2^64 - 1 is not supported");
   h->nslots = nslots;
   h->have_volume = true;
   const size_t want = std::min<size_t>(cap, nslots);
   U_OK(ensure(h->aux0, want * 8));
   U_OK(ensure(h->aux1, want * 8));
-  hipLaunchKernelGGL(label_compact_kernel, dim3((nslots + 255) / 256),
+  hipLaunchKernelGGL(table_compact_kernel<u64>, dim3((nslots + 255) / 256),
                      dim3(256), 0, h->stream,
                      static_cast<const u64*>(h->keys.p),
                      static_cast<const u64*>(h->table_counts.p), nslots,
                      static_cast<u64*>(h->aux0.p), static_cast<u64*>(h->aux1.p),
-                     (u32)want, n_out);
+                     static_cast<u32*>(nullptr), (u32)want, n_out);
   U_TRY(hipGetLastError());
   u32 found = 0;
   U_TRY(hipMemcpyAsync(&found, n_out, sizeof(u32), hipMemcpyDeviceToHost,

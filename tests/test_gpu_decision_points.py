@@ -298,3 +298,31 @@ def test_points_feed_process_many(fib25_model, tmp_path):
   want = sorted('%d-%d_at_%d_%d_%d.npz' % (a, b, *chosen[(a, b)][1])
                 for a, b in chosen)
   assert written == want
+
+
+def test_more_pairs_than_the_first_table():
+  """Every voxel an id of its own: more distinct pairs than the 2^18 slots the
+  pair table starts with, so it has to grow, and 4,096 voxels per block against
+  1,024 block-local slots, so most candidates go straight to the global table."""
+  from ffn_amd import decision
+  rng = np.random.default_rng(7)
+  shape = (48, 48, 48)
+  seg = (rng.permutation(48**3) + 1).astype(np.uint32).reshape(shape)
+  seg[rng.random(shape) < 0.3] = 0
+  voxel_size = (8, 8, 33)
+  want = decision_ref.minimising_spec(
+      decision_ref.candidates_spec(*decision_ref.expand_spec(seg, voxel_size)))
+  pairs = np.unique(np.stack([want['a'], want['b']]), axis=1).shape[1]
+  assert pairs > 1 << 18
+  fresh = decision.DecisionOps(0)  # a table no earlier test has grown
+  try:
+    fresh.expand(seg, voxel_size)
+    got = fresh.contact_minima()
+  finally:
+    fresh.close()
+  keys = ('a', 'b', 'off', 'z', 'y', 'x')
+  got_order = np.lexsort([got[j] for j in keys[::-1]])
+  want_order = np.lexsort([want[j] for j in keys[::-1]])
+  for k in keys:
+    assert np.array_equal(got[k][got_order], want[k][want_order])
+  assert got['dist'][got_order].tobytes() == want['dist'][want_order].tobytes()

@@ -201,6 +201,37 @@ def test_results_do_not_depend_on_what_ran_before(ops):
   assert ms > 0 and nbytes == small.size * 4 + again.size
 
 
+@pytest.mark.parametrize('dtype', [np.uint64, np.uint32])
+def test_more_ids_than_the_first_table(dtype):
+  """label_sizes with more distinct ids than the 2^18 slots the id table starts
+  with (it has to grow), long runs and one large count; then a small volume on
+  the same handle, which finds the grown table."""
+  from ffn_amd import partitions
+  rng = np.random.default_rng(70)
+  ids = rng.permutation(70**3).astype(np.uint64)
+  ids = ids * 2**33 + 5 if dtype == np.uint64 else ids + 1
+  seg = ids.astype(dtype).reshape(70, 70, 70)
+  seg[:4] = 9
+  want_ids, want_sizes = np.unique(seg, return_counts=True)
+  assert want_ids.size > 1 << 18
+  case = CASES[sorted(CASES)[0]]
+  fresh = partitions.PartitionOps(0)  # a table no earlier test has grown
+  try:
+    got_ids, got_sizes = fresh.label_sizes(seg)
+    order = np.argsort(got_ids)
+    assert np.array_equal(got_ids[order], want_ids.astype(np.uint64))
+    assert np.array_equal(got_sizes[order], want_sizes.astype(np.uint64))
+    got_ids, got_sizes = fresh.label_sizes(case['seg'])
+    order = np.argsort(got_ids)
+    want_ids, want_sizes = np.unique(case['seg'], return_counts=True)
+    assert np.array_equal(got_ids[order], want_ids.astype(np.uint64))
+    assert np.array_equal(got_sizes[order], want_sizes.astype(np.uint64))
+    got = fresh.compute(case['seg'], mask=case['mask'], **case_args(case))
+    assert got.tobytes() == case['partitions'].tobytes()
+  finally:
+    fresh.close()
+
+
 def test_cli_end_to_end(tmp_path):
   import compute_partitions as root
   case = CASES['excl']
