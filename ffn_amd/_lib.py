@@ -25,10 +25,11 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_analysis.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
            'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip',
-           'ffn_evaluation.hip']
+           'ffn_evaluation.hip', 'ffn_gradients.hip']
 
 MAX_CANDIDATES = 16
 
@@ -384,6 +385,20 @@ SIGNATURES = {
     'ffn_evaluation_write_seed': (_I, [_P, _I, _P]),
     'ffn_evaluation_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_gradients.h
+    'ffn_gradients_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_gradients_destroy': (None, [_P]),
+    'ffn_gradients_conv_forward': (_I, [_P, _I, _I3, _I, _P, _P, _I, _P, _P, _P,
+                                        _P]),
+    'ffn_gradients_conv_backward_input': (_I, [_P, _I, _I3, _P, _P, _P, _I,
+                                               _P]),
+    'ffn_gradients_conv_backward_weights': (_I, [_P, _I, _I3, _I, _P, _P, _I,
+                                                 _P, _P, _P]),
+    'ffn_gradients_head_forward': (_I, [_P, _I, _I3, _P, _P, _P, _P, _P]),
+    'ffn_gradients_head_backward': (_I, [_P, _I, _I3, _P, _P, _P, _P, _P, _P]),
+    'ffn_gradients_loss': (_I, [_P, _I, _I3, _P, _P, _P,
+                                ctypes.POINTER(ctypes.c_float), _P]),
+    'ffn_gradients_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None
