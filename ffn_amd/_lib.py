@@ -26,10 +26,11 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_partitions.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_optimizer.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
            'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip',
-           'ffn_evaluation.hip', 'ffn_gradients.hip']
+           'ffn_evaluation.hip', 'ffn_gradients.hip', 'ffn_optimizer.hip']
 
 MAX_CANDIDATES = 16
 
@@ -399,6 +400,17 @@ SIGNATURES = {
     'ffn_gradients_loss': (_I, [_P, _I, _I3, _P, _P, _P,
                                 ctypes.POINTER(ctypes.c_float), _P]),
     'ffn_gradients_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_optimizer.h
+    'ffn_optimizer_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_optimizer_destroy': (None, [_P]),
+    'ffn_optimizer_grad_stats': (_I, [_P, ctypes.c_int64, _P, ctypes.c_float,
+                                      ctypes.POINTER(ctypes.c_float),
+                                      ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint64)]),
+    'ffn_optimizer_apply': (_I, [_P, _I, ctypes.c_int64, _P, _P, _P, _P,
+                                 ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 ctypes.c_float, ctypes.c_float]),
+    'ffn_optimizer_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

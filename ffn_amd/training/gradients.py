@@ -9,8 +9,10 @@ pixelwise loss with its logit gradient, as device-to-device calls.
 convstack_3d.py:38-54, and backwards in reverse): for a batch of training FoVs
 it returns the loss and its gradient with respect to every variable of the
 model.  The contractions, reductions and the loss run in the unit only; torch
-owns the device buffers and moves data, nothing else.  There is no optimizer
-here, no train.py and no CPU fallback: without a GPU the constructors raise.
+owns the device buffers and moves data, nothing else.  The parameter update
+is trainer.ConvStackTrainer's, which hands this class its weight and gradient
+storage and leaves the gradients on the device; there is no CPU fallback:
+without a GPU the constructors raise.
 """
 
 from __future__ import annotations
@@ -109,9 +111,16 @@ def default_ops(device_id: int = 0) -> GradientOps:
 class ConvStackGradients:
   """Loss and gradients of a ConvStack3DFFNModel (any depth >= 2, 32 features,
   any FoV) for up to `max_batch` FoVs per call; the weights and every buffer
-  live on device `device_id`."""
+  live on device `device_id`.
 
-  def __init__(self, model, max_batch: int = 1, device_id: int = 0):
+  `storage`, if given, is {'w', 'b', 'dw', 'db'}: per kind a dict scope -> flat
+  f32 device tensor of the variable's size, 16-byte aligned.  The object then
+  reads its weights from and writes its gradients to these tensors (views into
+  a trainer's arenas) instead of allocating its own, and the caller keeps them
+  current; the weights are not uploaded from the model."""
+
+  def __init__(self, model, max_batch: int = 1, device_id: int = 0,
+               storage=None):
     if model.variables is None:
       raise ValueError('model has no weights (load_checkpoint / init_random)')
     if model.features != FEATURES:
@@ -132,7 +141,11 @@ class ConvStackGradients:
     self.shapes = {}
     self.w = {}
     self.b = {}
-    self.set_variables(model.variables)
+    self._dw = self._db = None
+    if storage is None:
+      self.set_variables(model.variables)
+    else:
+      self._adopt(model.variables, storage)
     self._buffers = None
     self._key = None
 
@@ -144,8 +157,29 @@ class ConvStackGradients:
         name = 'seed_update/%s/%s' % (scope, kind)
         host = np.ascontiguousarray(variables[name], dtype=np.float32)
         self.shapes[name] = host.shape
-        store[scope] = torch.from_numpy(host.reshape(-1).copy()).to(self.device)
+        flat = torch.from_numpy(host.reshape(-1).copy())
+        if self._dw is None:
+          store[scope] = flat.to(self.device)
+        else:  # handed storage: in place, the views stay what they are
+          store[scope].copy_(flat)
     torch.cuda.synchronize(self.device)
+
+  def _adopt(self, variables, storage):
+    torch = self.torch
+    for scope in self.scopes:
+      for kind, key in (('weights', 'w'), ('biases', 'b')):
+        name = 'seed_update/%s/%s' % (scope, kind)
+        self.shapes[name] = tuple(np.shape(variables[name]))
+        size = int(np.prod(self.shapes[name]))
+        for k in (key, 'd' + key):
+          t = storage[k][scope]
+          if (t.dtype != torch.float32 or t.device != self.device or
+              tuple(t.shape) != (size,) or not t.is_contiguous() or
+              t.data_ptr() % 16):
+            raise ValueError('storage[%r][%r]: expected %d dense f32 on %s, '
+                             '16-byte aligned' % (k, scope, size, self.device))
+    self.w, self.b = dict(storage['w']), dict(storage['b'])
+    self._dw, self._db = dict(storage['dw']), dict(storage['db'])
 
   def close(self):
     self.ops.close()
@@ -173,8 +207,8 @@ class ConvStackGradients:
         'pre': [new(act) for _ in range(2 * self.depth)],
         'g': new(act), 't': new(act),
         'logits': new(key), 'dlogits': new(key),
-        'dw': {s: new(self.w[s].shape) for s in self.scopes},
-        'db': {s: new(self.b[s].shape) for s in self.scopes},
+        'dw': self._dw or {s: new(self.w[s].shape) for s in self.scopes},
+        'db': self._db or {s: new(self.b[s].shape) for s in self.scopes},
     }
     self._buffers, self._key = buf, key
     return buf
@@ -191,6 +225,27 @@ class ConvStackGradients:
     order (conv0_a's output, then per residual block its incoming stream and
     conv_i_a's output, then the final stream: 2 * depth arrays
     [n, z, y, x, 32]).  All returned arrays are numpy."""
+    loss, buf = self._run(seed, image, labels, weights)
+    dw, db = buf['dw'], buf['db']
+    grads = {}
+    for scope in self.scopes:
+      for kind, store in (('weights', dw), ('biases', db)):
+        name = 'seed_update/%s/%s' % (scope, kind)
+        grads[name] = store[scope].cpu().numpy().reshape(self.shapes[name])
+    logits = buf['logits'].cpu().numpy()
+    if return_pre_activations:
+      return loss, logits, grads, [p.cpu().numpy() for p in buf['pre']]
+    return loss, logits, grads
+
+  def loss_and_gradients_device(self, seed, image, labels, weights):
+    """The same calls; returns (loss, logits) with logits a device tensor
+    [n, z, y, x] that the next call overwrites.  The gradients stay on the
+    device: in the handed storage, or in this object's own buffers."""
+    loss, buf = self._run(seed, image, labels, weights)
+    return loss, buf['logits']
+
+  def _run(self, seed, image, labels, weights):
+    """Forward and backward through the unit; returns (loss, buffers)."""
     shape4 = tuple(int(v) for v in np.shape(seed))
     if len(shape4) != 4:
       raise ValueError('expected [n, z, y, x] arrays, got shape %r' % (shape4,))
@@ -242,13 +297,4 @@ class ConvStackGradients:
     ops.conv_backward_input(n, zyx, g, w['conv0_b'], pre[0], False, t)
     ops.conv_backward_weights(n, zyx, 2, image_d, seed_d, False, t,
                               dw['conv0_a'], db['conv0_a'])
-
-    grads = {}
-    for scope in self.scopes:
-      for kind, store in (('weights', dw), ('biases', db)):
-        name = 'seed_update/%s/%s' % (scope, kind)
-        grads[name] = store[scope].cpu().numpy().reshape(self.shapes[name])
-    logits = buf['logits'].cpu().numpy()
-    if return_pre_activations:
-      return loss, logits, grads, [p.cpu().numpy() for p in pre]
-    return loss, logits, grads
+    return loss, buf
