@@ -290,6 +290,21 @@ struct ffn_engine {
   void* h_scratch = nullptr;
   size_t scratch_bytes = 0;
 
+  // The segment turn's own scratch (ffn_canvas_segment_turn, ffn_canvas_commit_count;
+  // under util_mu, on the utility stream).  d_turn: [TurnRecord][partials: kTurnBlocks
+  // pairs][flags, seed, seg: 4 bytes, voxel index: 8 bytes, turn_ncap each][histogram:
+  // turn_hcap words].  The histogram is zeroed when it is allocated and every turn's
+  // last kernel leaves it zero again (turn_hist_clean: false while a turn is under way
+  // or after one that failed -- the next one zeroes it first).  h_turn: pinned and
+  // device-mapped, 8-byte words: [candidates, 3 turn_ncap int32][published: 8 +
+  // 3 turn_ncap + 2 turn_ocap words, upper half = turn_seq of the turn that wrote it].
+  void* d_turn = nullptr;
+  unsigned long long* h_turn = nullptr;
+  unsigned long long* h_turn_dev = nullptr;  // h_turn as the device addresses it
+  size_t turn_ncap = 0, turn_hcap = 0, turn_ocap = 0;
+  bool turn_hist_clean = false;
+  unsigned turn_seq = 0;
+
   int prof_mode = 0;
   std::vector<hipEvent_t> events;
   int events_used = 0;
@@ -444,6 +459,46 @@ struct UtilLock {
     if (err == hipSuccess) c->util_pending = false;  // done: nothing to wait for
     return err;
   }
+  // ... or, where the call's last kernel publishes what the call returns into pinned
+  // memory (turn_publish_kernel), poll for it instead of blocking on the stream (`mu`
+  // released meanwhile).  arrived(): every published word carries this call's number.
+  // Bounded, and as ffn_canvas_step_wait polls: no hipStreamQuery in the loop (on a busy
+  // stream it puts a barrier packet into the queue), the stream is asked only after 2 ms
+  // without the record, then every 2 ms, so that a device fault still surfaces as an error.
+  // That last kernel runs behind everything the call queued, so the canvas is left as a
+  // completed wait() leaves it: nothing pending, and ev_util -- not recorded again here --
+  // complete, since whatever recorded it last ran earlier on the same stream.
+  template <typename Arrived>
+  hipError_t wait_published(ffn_engine* e, ffn_canvas* c, Arrived arrived) {
+    if (e->sync_mode != 1) {
+      const hipError_t err = wait(e, c);
+      if (err != hipSuccess) return err;
+      return arrived() ? hipSuccess : hipErrorUnknown;
+    }
+    lk.unlock();
+    bool done = false;
+    long long t_first = 0, t_query = 0;
+    for (long spin = 0; !done; ++spin) {
+      done = arrived();
+      if (!done && (spin & 0xfff) == 0xfff) {
+        const long long now = steady_ns();
+        if (t_first == 0) t_first = t_query = now;
+        if (now - t_first > 10000000000LL) break;  // 10 s: let the stream say what happened
+        if (now - t_query > 2000000) {
+          t_query = now;
+          if (hipStreamQuery(e->ustream) != hipErrorNotReady) break;  // drained, or an error
+        }
+      }
+    }
+    hipError_t err = hipSuccess;
+    if (!done) {
+      err = hipStreamSynchronize(e->ustream);
+      if (err == hipSuccess && !arrived()) err = hipErrorUnknown;  // the kernel died
+    }
+    lk.lock();
+    if (err == hipSuccess) c->util_pending = false;
+    return err;
+  }
 };
 // host-side: nothing queued on canvas c is still running
 hipError_t canvas_quiesce(ffn_engine* e, ffn_canvas* c) {
@@ -499,6 +554,92 @@ int ensure_scratch(ffn_engine* e, size_t bytes) {
   e->scratch_bytes = want;
   return FFN_OK;
 }
+
+// ffn_engine::d_turn / h_turn for n candidates, a histogram of hist_n bins and
+// up to novl published overlap pairs
+struct TurnLayout {
+  size_t o_part, o_flag, o_hist, d_bytes;  // d_turn, bytes
+  size_t w_pub, h_words;                   // h_turn, 8-byte words
+  TurnLayout(size_t ncap, size_t hcap, size_t ocap) {
+    o_part = sizeof(TurnRecord);
+    o_flag = o_part + (size_t)kTurnBlocks * 16;
+    o_hist = o_flag + 20 * ncap;
+    d_bytes = o_hist + 4 * hcap;
+    w_pub = 3 * ncap / 2;
+    h_words = w_pub + 8 + 3 * ncap + 2 * ocap;
+  }
+};
+
+int ensure_turn(ffn_engine* e, size_t n, size_t hist_n, size_t novl) {
+  if (n > e->turn_ncap || hist_n > e->turn_hcap || novl > e->turn_ocap) {
+    HIP_TRY(hipStreamSynchronize(e->ustream));  // (only utility calls use it)
+    if (e->d_turn) HIP_TRY(hipFree(e->d_turn));
+    if (e->h_turn) HIP_TRY(hipHostFree(e->h_turn));
+    e->d_turn = nullptr;
+    e->h_turn = e->h_turn_dev = nullptr;
+    const size_t ncap = (std::max<size_t>({n, e->turn_ncap, 256}) + 3) & ~(size_t)3;
+    const size_t hcap = std::max<size_t>({hist_n, e->turn_hcap, (size_t)kTurnHistLds});
+    const size_t ocap = std::max<size_t>({novl, e->turn_ocap, 1024});
+    e->turn_ncap = e->turn_hcap = e->turn_ocap = 0;
+    const TurnLayout lay(ncap, hcap, ocap);
+    HIP_TRY(hipMalloc(&e->d_turn, lay.d_bytes));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_turn), lay.h_words * 8,
+                          hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(e->h_turn, 0, lay.h_words * 8);  // no word carries a live turn's number
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_turn_dev), e->h_turn, 0));
+    e->turn_ncap = ncap;
+    e->turn_hcap = hcap;
+    e->turn_ocap = ocap;
+    e->turn_hist_clean = false;
+  }
+  if (!e->turn_hist_clean) {
+    // newly allocated, grown, or left behind by a turn that failed: zeroed here, once
+    const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
+    HIP_TRY(hipMemsetAsync(static_cast<char*>(e->d_turn) + lay.o_hist, 0,
+                           4 * e->turn_hcap, e->ustream));
+  }
+  e->turn_hist_clean = false;  // until this turn's publish kernel has run
+  return FFN_OK;
+}
+
+// for_box_rows: log2 of the lanes a row of nx voxels gets (1 .. 64 of them)
+int row_lanes_log2(int nx) {
+  int xs = 0;
+  while (xs < 6 && (1 << xs) < nx) ++xs;
+  return xs;
+}
+
+// the grid of a for_box_rows sweep: 4 waves per block, 64 >> xs rows per wave pass
+int turn_grid(long rows, int xs) {
+  const long per_block = 4 * (64 >> xs);
+  return (int)std::max<long>(1, std::min<long>((rows + per_block - 1) / per_block,
+                                               kTurnBlocks));
+}
+
+// What turn_publish_kernel wrote for call `seq`, n candidates: words whose upper half
+// is seq have arrived (see the kernel for the layout).
+struct TurnPub {
+  const unsigned long long* w;
+  unsigned seq;
+  size_t n;
+  uint32_t at(size_t k) const { return (uint32_t)__atomic_load_n(&w[k], __ATOMIC_RELAXED); }
+  bool has(size_t first, size_t count) const {
+    for (size_t k = first; k < first + count; ++k)
+      if ((unsigned)(__atomic_load_n(&w[k], __ATOMIC_ACQUIRE) >> 32) != seq) return false;
+    return true;
+  }
+  // the header says how many pairs follow the candidates' words
+  bool arrived() const { return has(0, 8 + 3 * n) && has(8 + 3 * n, 2 * (size_t)at(7)); }
+  // into the caller's arrays; returns the exact number of overlapped ids
+  int overlaps(int32_t* ids, int64_t* counts) const {
+    const size_t o = 8 + 3 * n;
+    for (size_t k = 0; k < at(7); ++k) {
+      ids[k] = (int32_t)at(o + 2 * k);
+      counts[k] = (int64_t)at(o + 2 * k + 1);
+    }
+    return (int)at(6);
+  }
+};
 
 template <bool RI, bool RO, bool SK>
 int set_lds_attr(size_t bytes) {
@@ -1784,6 +1925,8 @@ void ffn_engine_destroy(ffn_engine* e) {
   (void)hipFree(e->weights);
   (void)hipFree(e->d_items);
   (void)hipFree(e->d_scratch);
+  (void)hipFree(e->d_turn);
+  if (e->h_turn) (void)hipHostFree(e->h_turn);
   if (e->h_io) (void)hipHostFree(e->h_io);
   if (e->h_items) (void)hipHostFree(e->h_items);
   if (e->h_pub) (void)hipHostFree(e->h_pub);
@@ -3514,38 +3657,36 @@ int ffn_canvas_commit_count(ffn_canvas* c, const int32_t lo[3],
   if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(lock_.begin(e, c));
-  const size_t hist_n = (size_t)max_existing_id + 1;
-  const size_t bytes = 16 + hist_n * sizeof(unsigned);
-  rc = ensure_scratch(e, bytes);
+  // the turn's count and publish kernels: two launches, the answer polled
+  const int novl = overlap_ids && overlap_counts
+                       ? std::max(std::min(max_overlaps, max_existing_id), 0) : 0;
+  rc = ensure_turn(e, 0, (size_t)max_existing_id + 1, (size_t)novl);
   if (rc) return rc;
+  const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
+  char* ds = static_cast<char*>(e->d_turn);
+  auto* d_part = reinterpret_cast<unsigned long long*>(ds + lay.o_part);
+  auto* d_hist = reinterpret_cast<unsigned*>(ds + lay.o_hist);
+  if (++e->turn_seq == 0) ++e->turn_seq;
   long total;
   Box b = make_box(c, lo, hi, &total);
-  HIP_TRY(hipMemsetAsync(e->d_scratch, 0, bytes, e->ustream));
-  auto* d_counts = static_cast<unsigned long long*>(e->d_scratch);
-  auto* d_hist = reinterpret_cast<unsigned*>(static_cast<char*>(e->d_scratch) + 16);
-  if (total > 0)
-    hipLaunchKernelGGL(commit_count_kernel, dim3(grid_for(total)), dim3(256), 0,
-                       e->ustream, c->seed, c->seg, b, total, segment_threshold,
-                       max_existing_id, d_counts, d_hist);
-  HIP_TRY(hipMemcpyAsync(e->h_scratch, e->d_scratch, bytes, hipMemcpyDeviceToHost,
-                         e->ustream));
-  HIP_TRY(lock_.wait(e, c));
-  const auto* hc = static_cast<const unsigned long long*>(e->h_scratch);
-  const auto* hh = reinterpret_cast<const unsigned*>(
-      static_cast<const char*>(e->h_scratch) + 16);
-  counts->raw_segmented_voxels = (int64_t)hc[0];
-  counts->actual_segmented_voxels = (int64_t)hc[1];
-  int nover = 0;
-  for (size_t id = 1; id < hist_n; ++id) {
-    if (hh[id]) {
-      if (nover < max_overlaps && overlap_ids && overlap_counts) {
-        overlap_ids[nover] = (int32_t)id;
-        overlap_counts[nover] = (int64_t)hh[id];
-      }
-      ++nover;
-    }
-  }
-  counts->num_overlapped_ids = nover;
+  const long rows = total > 0 ? (long)b.n[0] * b.n[1] : 0;
+  const int xs = row_lanes_log2(b.n[2]);
+  const int nparts = rows > 0 ? turn_grid(rows, xs) : 0;
+  if (nparts > 0)
+    hipLaunchKernelGGL(turn_count_kernel, dim3(nparts), dim3(256), 0, e->ustream, c->seed,
+                       c->seg, b, rows, xs, segment_threshold, max_existing_id,
+                       max_existing_id < kTurnHistLds ? 1 : 0, d_part, d_hist);
+  hipLaunchKernelGGL(turn_publish_kernel, dim3(1), dim3(1024), 0, e->ustream,
+                     reinterpret_cast<const TurnRecord*>(ds), d_part, nparts, d_hist,
+                     max_existing_id, novl, nullptr, nullptr, nullptr, 0, 0, 0,
+                     e->h_turn_dev + lay.w_pub, e->turn_seq);
+  HIP_TRY(hipGetLastError());
+  const TurnPub pub{e->h_turn + lay.w_pub, e->turn_seq, 0};
+  HIP_TRY(lock_.wait_published(e, c, [&] { return pub.arrived(); }));
+  e->turn_hist_clean = true;
+  counts->raw_segmented_voxels = (int64_t)(pub.at(0) | (uint64_t)pub.at(1) << 32);
+  counts->actual_segmented_voxels = (int64_t)(pub.at(2) | (uint64_t)pub.at(3) << 32);
+  counts->num_overlapped_ids = pub.overlaps(overlap_ids, overlap_counts);
   return FFN_OK;
 }
 
@@ -3598,102 +3739,95 @@ int ffn_canvas_segment_turn(ffn_canvas* c, const ffn_turn_request* rq,
   HIP_TRY(hipSetDevice(e->device));
   const long long t_turn0 = steady_ns();
   HIP_TRY(lock_.begin(e, c));
-  // scratch: [record][histogram][flags, seeds, segs: n each][candidates: 3 n]
   const int32_t max_id = rq->do_commit ? std::max(rq->max_existing_id, 0) : 0;
-  const size_t hist_n = rq->do_commit ? (size_t)max_id + 1 : 0;
-  const size_t o_hist = sizeof(TurnRecord);
-  const size_t o_flag = (o_hist + hist_n * 4 + 15) & ~(size_t)15;
-  const size_t o_cand = o_flag + 12 * (size_t)n;
-  const size_t bytes = o_cand + 12 * (size_t)n;
-  rc = ensure_scratch(e, bytes);
+  const int novl = rq->do_commit && overlap_ids && overlap_counts
+                       ? std::max(std::min(max_overlaps, max_id), 0) : 0;
+  rc = ensure_turn(e, (size_t)n, (size_t)max_id + 1, (size_t)novl);
   if (rc) return rc;
-  char* ds = static_cast<char*>(e->d_scratch);
-  char* hs = static_cast<char*>(e->h_scratch);
+  const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
+  char* ds = static_cast<char*>(e->d_turn);
+  const size_t ncap = e->turn_ncap;
   auto* d_rec = reinterpret_cast<TurnRecord*>(ds);
-  auto* d_hist = reinterpret_cast<unsigned*>(ds + o_hist);
-  auto* d_flag = reinterpret_cast<int*>(ds + o_flag);
-  auto* d_cseed = reinterpret_cast<float*>(ds + o_flag + 4 * (size_t)n);
-  auto* d_cseg = reinterpret_cast<int32_t*>(ds + o_flag + 8 * (size_t)n);
-  auto* d_cand = reinterpret_cast<int32_t*>(ds + o_cand);
-  // (chosen = -1 until the pick kernel has run: all-ones bytes)
-  HIP_TRY(hipMemsetAsync(ds, 0, o_flag, e->ustream));
-  HIP_TRY(hipMemsetAsync(&d_rec->chosen, 0xff, 4, e->ustream));
-  if (n > 0) {
-    std::memcpy(hs + o_cand, cand, 12 * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(d_cand, hs + o_cand, 12 * (size_t)n, hipMemcpyHostToDevice,
-                           e->ustream));
-  }
+  auto* d_part = reinterpret_cast<unsigned long long*>(ds + lay.o_part);
+  auto* d_flag = reinterpret_cast<int*>(ds + lay.o_flag);
+  auto* d_cseed = reinterpret_cast<float*>(ds + lay.o_flag + 4 * ncap);
+  auto* d_cseg = reinterpret_cast<int32_t*>(ds + lay.o_flag + 8 * ncap);
+  auto* d_ci = reinterpret_cast<size_t*>(ds + lay.o_flag + 12 * ncap);
+  auto* d_hist = reinterpret_cast<unsigned*>(ds + lay.o_hist);
+  if (++e->turn_seq == 0) ++e->turn_seq;
+  // the candidates reach the device without a copy operation: the evaluate kernel reads
+  // the pinned buffer (the call does not return before the turn has run, so one buffer)
+  if (n > 0) std::memcpy(e->h_turn, cand, 12 * (size_t)n);
   long total = 0;
-  Box b{};
-  if (rq->do_commit) {
-    b = make_box(c, rq->lo, rq->hi, &total);
-    if (total > 0)
-      hipLaunchKernelGGL(commit_count_kernel, dim3(grid_for(total)), dim3(256), 0,
-                         e->ustream, c->seed, c->seg, b, total, rq->segment_threshold,
-                         max_id, d_rec->counts, d_hist);
+  Box b = make_box(c, rq->lo, rq->hi, &total);
+  if (!rq->do_commit) {
+    total = 0;
+    b.n[0] = b.n[1] = b.n[2] = 0;
   }
-  if (rq->do_commit || rq->mark_mode) {
-    const long mark_ci =
-        rq->mark_mode ? ((long)rq->mark_pos[0] * c->cy + rq->mark_pos[1]) * c->cx +
-                            rq->mark_pos[2]
-                      : 0;
-    hipLaunchKernelGGL(turn_commit_kernel, dim3(total > 0 ? grid_for(total) : 1),
-                       dim3(256), 0, e->ustream, c->seed, c->seg, b, total,
-                       rq->segment_threshold, rq->segment_id,
-                       (long long)rq->min_segment_size, d_rec, mark_ci, rq->mark_mode);
-  }
-  long dirty_total = 0;
+  const long rows = total > 0 ? (long)b.n[0] * b.n[1] : 0;
+  const int xs = row_lanes_log2(b.n[2]);
+  const int nparts = rows > 0 ? turn_grid(rows, xs) : 0;
+  const bool has_commit = rq->do_commit || rq->mark_mode;
+  if (nparts > 0)
+    hipLaunchKernelGGL(turn_count_kernel, dim3(nparts), dim3(256), 0, e->ustream, c->seed,
+                       c->seg, b, rows, xs, rq->segment_threshold, max_id,
+                       max_id < kTurnHistLds ? 1 : 0, d_part, d_hist);
+  if (has_commit)
+    hipLaunchKernelGGL(turn_commit_kernel, dim3(std::max(nparts, 1)), dim3(256), 0,
+                       e->ustream, c->seed, c->seg, b, rows, xs, rq->segment_threshold,
+                       rq->segment_id, (long long)rq->min_segment_size, d_part, nparts,
+                       d_rec, rq->mark_pos[0], rq->mark_pos[1], rq->mark_pos[2],
+                       rq->mark_mode);
   if (n > 0) {
     hipLaunchKernelGGL(turn_eval_kernel, dim3(n), dim3(64), 0, e->ustream, c->seed,
-                       c->seg, c->cz, c->cy, c->cx, d_cand, rq->min_boundary_dist[0],
-                       rq->min_boundary_dist[1], rq->min_boundary_dist[2], d_flag,
-                       d_cseed, d_cseg, c->restrict_planes, c->restrict_plane_words,
-                       c->restrict_row_words);
-    hipLaunchKernelGGL(turn_pick_kernel, dim3(1), dim3(64), 0, e->ustream, c->seg,
-                       c->cy, c->cx, d_cand, n, d_flag, d_rec);
-    if (rq->do_init) {
-      if (c->dirty_lo[0] < c->dirty_hi[0]) {
-        Box db = make_box(c, c->dirty_lo, c->dirty_hi, &dirty_total);
-        const int linear = (size_t)dirty_total * 2 >= c->nvox;
-        if (dirty_total > 0)
-          hipLaunchKernelGGL(turn_clear_kernel,
-                             dim3(linear ? 2048 : grid_for(dirty_total)), dim3(256), 0,
-                             e->ustream, reinterpret_cast<uint32_t*>(c->seed), db,
-                             dirty_total, linear, c->nvox, d_rec);
-      }
-      hipLaunchKernelGGL(turn_seed_kernel, dim3(1), dim3(1), 0, e->ustream, c->seed,
-                         c->cy, c->cx, d_cand, rq->init_value, d_rec);
+                       c->seg, c->cz, c->cy, c->cx,
+                       reinterpret_cast<const int32_t*>(e->h_turn_dev),
+                       rq->min_boundary_dist[0], rq->min_boundary_dist[1],
+                       rq->min_boundary_dist[2], d_flag, d_cseed, d_cseg, d_ci,
+                       c->restrict_planes, c->restrict_plane_words, c->restrict_row_words);
+    // pick, and init_seed at the one picked: the dirty box (or, from half the volume on,
+    // everything) back to NaN and the seed point, in the same launch
+    long dirty_total = 0;
+    Box db = make_box(c, c->dirty_lo, c->dirty_hi, &dirty_total);
+    if (!rq->do_init || c->dirty_lo[0] >= c->dirty_hi[0] || dirty_total <= 0) {
+      dirty_total = 0;
+      db.n[0] = db.n[1] = db.n[2] = 0;
     }
+    const long drows = dirty_total > 0 ? (long)db.n[0] * db.n[1] : 0;
+    const int dxs = row_lanes_log2(db.n[2]);
+    const int clear = !rq->do_init ? 0 : (size_t)dirty_total * 2 >= c->nvox ? 2 : 1;
+    const int grid = clear == 2 ? 2048 : clear == 1 ? turn_grid(drows, dxs) : 1;
+    uint32_t init_bits;
+    std::memcpy(&init_bits, &rq->init_value, 4);
+    hipLaunchKernelGGL(turn_pick_clear_kernel, dim3(grid), dim3(256), 0, e->ustream,
+                       reinterpret_cast<uint32_t*>(c->seed), c->seg, d_flag, d_ci, n,
+                       d_rec, db, drows, dxs, clear, c->nvox, init_bits);
   }
+  hipLaunchKernelGGL(turn_publish_kernel, dim3(1), dim3(1024), 0, e->ustream, d_rec,
+                     d_part, 0, d_hist, max_id, novl, d_flag, d_cseed, d_cseg, n,
+                     has_commit ? 1 : 0, n > 0 ? 1 : 0, e->h_turn_dev + lay.w_pub,
+                     e->turn_seq);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(hs, ds, o_cand, hipMemcpyDeviceToHost, e->ustream));
   const long long t_turn1 = steady_ns();
-  HIP_TRY(lock_.wait(e, c));
+  const TurnPub pub{e->h_turn + lay.w_pub, e->turn_seq, (size_t)n};
+  HIP_TRY(lock_.wait_published(e, c, [&] { return pub.arrived(); }));
+  e->turn_hist_clean = true;
   e->stat_segturn_queue_ns += t_turn1 - t_turn0;
   e->stat_segturn_wait_ns += steady_ns() - t_turn1;
   e->stat_segturn_calls += 1;
-  const auto* hr = reinterpret_cast<const TurnRecord*>(hs);
   std::memset(out, 0, sizeof(*out));
-  out->counts.raw_segmented_voxels = (int64_t)hr->counts[0];
-  out->counts.actual_segmented_voxels = (int64_t)hr->counts[1];
-  out->committed = hr->committed;
-  out->chosen = n > 0 ? hr->chosen : -1;
-  const auto* hh = reinterpret_cast<const unsigned*>(hs + o_hist);
-  int nover = 0;
-  for (size_t id = 1; id < hist_n; ++id) {
-    if (hh[id]) {
-      if (nover < max_overlaps && overlap_ids && overlap_counts) {
-        overlap_ids[nover] = (int32_t)id;
-        overlap_counts[nover] = (int64_t)hh[id];
-      }
-      ++nover;
-    }
-  }
-  out->counts.num_overlapped_ids = nover;
+  out->counts.raw_segmented_voxels = (int64_t)(pub.at(0) | (uint64_t)pub.at(1) << 32);
+  out->counts.actual_segmented_voxels = (int64_t)(pub.at(2) | (uint64_t)pub.at(3) << 32);
+  out->committed = (int32_t)pub.at(4);
+  out->chosen = (int32_t)pub.at(5);
+  out->counts.num_overlapped_ids = pub.overlaps(overlap_ids, overlap_counts);
   if (n > 0) {
-    std::memcpy(cand_flags, hs + o_flag, 4 * (size_t)n);
-    std::memcpy(cand_seed, hs + o_flag + 4 * (size_t)n, 4 * (size_t)n);
-    std::memcpy(cand_seg, hs + o_flag + 8 * (size_t)n, 4 * (size_t)n);
+    for (int k = 0; k < n; ++k) {
+      cand_flags[k] = (int32_t)pub.at(8 + (size_t)k);
+      const uint32_t sb = pub.at(8 + (size_t)n + k);
+      std::memcpy(&cand_seed[k], &sb, 4);
+      cand_seg[k] = (int32_t)pub.at(8 + 2 * (size_t)n + k);
+    }
     if (rq->do_init && out->chosen >= 0) {
       // as ffn_canvas_init_seed: the volume is clean but for the seed point
       const int32_t* p = cand + 3 * out->chosen;

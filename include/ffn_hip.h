@@ -288,7 +288,9 @@ int ffn_canvas_commit_assign(ffn_canvas* canvas, const int32_t lo[3],
                              int32_t segment_id);
 
 /* The between-segment turn of Canvas.segment_all (inference.py:573-660) as one
- * device-side sequence, one host wait at its end instead of one per question:
+ * device-side sequence (at most five kernel launches, no copy operation).  Its last
+ * kernel publishes the answers into pinned host memory and the call polls for them
+ * there, once, instead of waiting on the stream after every question:
  *   1. do_commit: the commit reduction over [lo, hi) (ffn_canvas_commit_count);
  *      if actual_segmented_voxels >= min_segment_size the voxels get segment_id
  *      (inference.py:614-646) and *committed = 1;
