@@ -386,6 +386,13 @@ SIGNATURES = {
     'ffn_evaluation_write_seed': (_I, [_P, _I, _P]),
     'ffn_evaluation_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_double)]),
+    'ffn_evaluation_load_augmented': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P,
+                                           ctypes.c_float, ctypes.c_float]),
+    'ffn_evaluation_gather_train': (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    'ffn_evaluation_io_labels': (_I, [_P, ctypes.POINTER(_P)]),
+    'ffn_evaluation_last_timing_train': (_I, [_P,
+                                              ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double)]),
     # include/ffn_gradients.h
     'ffn_gradients_create': (_I, [_I, ctypes.POINTER(_P)]),
     'ffn_gradients_destroy': (None, [_P]),

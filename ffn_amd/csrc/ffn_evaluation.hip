@@ -11,7 +11,10 @@
 // values.  finish runs at most kFinishBlocks workgroups: per-thread sums in
 // index order, a shuffle tree per wave, an LDS tree per workgroup, and a
 // second one-workgroup launch combines the workgroups' partials the same way,
-// so the f32 sum does not depend on timing.
+// so the f32 sum does not depend on timing.  load_augmented keeps load's rows
+// while x stays x; where x changes places with y or z it moves 64 x 64 tiles
+// through LDS (row stride 65) so that lanes run along the volume's x on the
+// read and along the slot's x on the write.
 //
 // The host validates every box against the geometry before a launch; the
 // kernels take the validated starts.  The per-call descriptors go through a
@@ -74,6 +77,27 @@ struct BoxItem {
   int slot;
   int a0[3];  // in the seed canvas
   int b0[3];  // in the image patch (gather) / label patch (probe)
+};
+
+// One entry of a load_augmented: the load, and the transform in the form the
+// kernel branches on.  x_moves = 0: x stays x (perm[2] == 2); `swap` says
+// whether z and y change places; ra / rb / rx are the reflections of output z,
+// y, x.  x_moves = 1: output axis a2 (0 or 1) takes the volume's x, the
+// slot's x comes from volume axis p2 (0 or 1), the third output axis b = 1 -
+// a2 from volume axis 1 - p2; ra / rb / rx reflect output a2, b, x.
+struct AugItem {
+  LoadItem load;
+  int x_moves;
+  int a2, p2, swap;
+  int ra, rb, rx;
+};
+
+// One entry of gather_train: BoxItem and the start in the label patch.
+struct TrainBoxItem {
+  int slot;
+  int a0[3];  // in the seed canvas
+  int b0[3];  // in the image patch
+  int c0[3];  // in the label patch
 };
 
 struct SlotArrays {
@@ -146,6 +170,153 @@ __global__ __launch_bounds__(kThreads) void load_kernel(
   }
 }
 
+constexpr int kTile = 64;              // voxels per tile edge: one wave's run
+constexpr int kTileStride = kTile + 1;  // f32 column reads: 2 cycles, not 64
+
+__device__ __forceinline__ int dim_of(const Dims& d, int a) {
+  return a == 0 ? d.z : (a == 1 ? d.y : d.x);
+}
+
+template <bool kLabels>
+__device__ __forceinline__ float load_value(const LoadItem& it, long long i,
+                                            u64 centre) {
+  if (kLabels) {
+    const u64 l = label_at(it.labels, it.label_elem, i);
+    return (l > 0 && l == centre) ? 0.95f : 0.05f;
+  }
+  const float v = it.image_elem == 1
+                      ? (float)static_cast<const u8*>(it.image)[i]
+                      : static_cast<const float*>(it.image)[i];
+  return (v - it.offset) / it.scale;
+}
+
+// x stays x: load_kernel's row of lanes, the source row picked through the
+// transform and a reflected x read backwards.  q = row of the output patch.
+template <bool kLabels>
+__device__ __forceinline__ void aug_row(const AugItem& a, const int start[3],
+                                        Dims S, int q, float* dst, u64 centre,
+                                        int lane) {
+  const int z = q / S.y, y = q - z * S.y;
+  const int j0 = a.ra ? S.z - 1 - z : z;
+  const int j1 = a.rb ? S.y - 1 - y : y;
+  const int k0 = a.swap ? j1 : j0, k1 = a.swap ? j0 : j1;
+  const long long src = (start[0] + k0) * a.load.sy +
+                        (start[1] + k1) * a.load.sx + start[2];
+  float* row = dst + (size_t)q * S.x;
+  for (int x = lane; x < S.x; x += 64) {
+    const int kx = a.rx ? S.x - 1 - x : x;
+    row[x] = load_value<kLabels>(a.load, src + kx, centre);
+  }
+}
+
+// x changes places: tile t of the patch goes through LDS.  A tile is one index
+// i_b of output axis b and kTile x kTile of (output x, output a2).  Reading,
+// a wave takes one output-x index per round and its lanes run along the
+// volume's x (output a2), values already normalised / turned into soft labels;
+// writing, a wave takes one a2 index per round and its lanes run along the
+// slot's x.  Both sides are contiguous runs of up to kTile voxels.
+template <bool kLabels>
+__device__ __forceinline__ void aug_tile(const AugItem& a, const int start[3],
+                                         Dims S, int t, float* dst, u64 centre,
+                                         float (*tile)[kTileStride], int wave,
+                                         int lane) {
+  const int b = 1 - a.a2;
+  const int Sa = dim_of(S, a.a2), Sb = dim_of(S, b);
+  const int na = (Sa + kTile - 1) / kTile, nx = (S.x + kTile - 1) / kTile;
+  const int ib = t / (na * nx);
+  const int rem = t - ib * (na * nx);
+  const int ta = (rem / nx) * kTile, tx = (rem % nx) * kTile;
+  const long long st_p2 = a.p2 == 0 ? a.load.sy : a.load.sx;
+  const long long st_pb = a.p2 == 0 ? a.load.sx : a.load.sy;
+  const int jb = a.rb ? Sb - 1 - ib : ib;
+  const long long base = start[0] * a.load.sy + start[1] * a.load.sx +
+                         start[2] + jb * st_pb;
+  const int ia_r = ta + lane;
+  const int k2 = a.ra ? Sa - 1 - ia_r : ia_r;
+#pragma unroll 4
+  for (int r = wave; r < kTile; r += kWaves) {
+    const int i2 = tx + r;
+    if (i2 < S.x && ia_r < Sa) {
+      const int j2 = a.rx ? S.x - 1 - i2 : i2;
+      tile[r][lane] = load_value<kLabels>(a.load, base + j2 * st_p2 + k2, centre);
+    }
+  }
+  __syncthreads();
+  const int i2_w = tx + lane;
+#pragma unroll 4
+  for (int c = wave; c < kTile; c += kWaves) {
+    const int ia = ta + c;
+    if (ia < Sa && i2_w < S.x) {
+      const int i0 = a.a2 == 0 ? ia : ib, i1 = a.a2 == 0 ? ib : ia;
+      dst[((size_t)i0 * S.y + i1) * S.x + i2_w] = tile[lane][c];
+    }
+  }
+  __syncthreads();
+}
+
+// grid.y = entry.  The branch on x_moves is uniform per workgroup.
+__global__ __launch_bounds__(kThreads) void load_augmented_kernel(
+    const AugItem* __restrict__ items, SlotArrays s, float pad_logit,
+    float centre_logit) {
+  __shared__ float tile[kTile][kTileStride];
+  const AugItem a = items[blockIdx.y];
+  const LoadItem& it = a.load;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const Dims ip = s.image_patch, lp = s.label_patch;
+  const int rc = s.canvas.z * s.canvas.y;
+  const u64 centre = label_at(
+      it.labels, it.label_elem,
+      (it.lab0[0] + lp.z / 2) * it.sy + (it.lab0[1] + lp.y / 2) * it.sx +
+          (it.lab0[2] + lp.x / 2));
+  float* image = s.image_of(it.slot);
+  float* labels = s.labels_of(it.slot);
+  float* seed = s.seed_of(it.slot);
+  if (!a.x_moves) {
+    const int ri = ip.z * ip.y, rl = lp.z * lp.y;
+    const int rows = ri + rl + rc;
+    for (int r = blockIdx.x * kWaves + wave; r < rows;
+         r += gridDim.x * kWaves) {
+      if (r < ri) {
+        aug_row<false>(a, it.img0, ip, r, image, centre, lane);
+      } else if (r < ri + rl) {
+        aug_row<true>(a, it.lab0, lp, r - ri, labels, centre, lane);
+      } else {
+        const int q = r - ri - rl;
+        const int z = q / s.canvas.y, y = q - z * s.canvas.y;
+        const bool mid = z == s.canvas.z / 2 && y == s.canvas.y / 2;
+        float* dst = seed + (size_t)q * s.canvas.x;
+        for (int x = lane; x < s.canvas.x; x += 64)
+          dst[x] = (mid && x == s.canvas.x / 2) ? centre_logit : pad_logit;
+      }
+    }
+    return;
+  }
+  const int b = 1 - a.a2;
+  const int ti = dim_of(ip, b) * ((dim_of(ip, a.a2) + kTile - 1) / kTile) *
+                 ((ip.x + kTile - 1) / kTile);
+  const int tl = dim_of(lp, b) * ((dim_of(lp, a.a2) + kTile - 1) / kTile) *
+                 ((lp.x + kTile - 1) / kTile);
+  const int units = ti + tl + (rc + kWaves - 1) / kWaves;
+  // (u depends on the workgroup only: every thread meets the same barriers)
+  for (int u = blockIdx.x; u < units; u += gridDim.x) {
+    if (u < ti) {
+      aug_tile<false>(a, it.img0, ip, u, image, centre, tile, wave, lane);
+    } else if (u < ti + tl) {
+      aug_tile<true>(a, it.lab0, lp, u - ti, labels, centre, tile, wave, lane);
+    } else {
+      const int q = (u - ti - tl) * kWaves + wave;
+      if (q < rc) {
+        const int z = q / s.canvas.y, y = q - z * s.canvas.y;
+        const bool mid = z == s.canvas.z / 2 && y == s.canvas.y / 2;
+        float* dst = seed + (size_t)q * s.canvas.x;
+        for (int x = lane; x < s.canvas.x; x += 64)
+          dst[x] = (mid && x == s.canvas.x / 2) ? centre_logit : pad_logit;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void probe_kernel(
     const BoxItem* __restrict__ items, u32 n, SlotArrays s, float seed_thr,
     float label_thr, u8* __restrict__ out) {
@@ -188,6 +359,49 @@ __global__ __launch_bounds__(kThreads) void gather_kernel(
       float* dst = image_out + blockIdx.y * fi.voxels() + (size_t)q * fi.x;
       for (int x = lane; x < fi.x; x += 64) dst[x] = src[x];
     }
+  }
+}
+
+// Rows [0, rs) of an entry are the seed box, [rs, rs + ri) the image box, the
+// others the pred_mask box of the label patch.
+__global__ __launch_bounds__(kThreads) void gather_train_kernel(
+    const TrainBoxItem* __restrict__ items, SlotArrays s, Dims fs, Dims fi,
+    Dims pm, float* __restrict__ seed_out, float* __restrict__ image_out,
+    float* __restrict__ labels_out) {
+  const TrainBoxItem it = items[blockIdx.y];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int rs = fs.z * fs.y, ri = fi.z * fi.y;
+  const int rows = rs + ri + pm.z * pm.y;
+  for (int r = blockIdx.x * kWaves + wave; r < rows; r += gridDim.x * kWaves) {
+    const float* src;
+    float* dst;
+    int nx;
+    if (r < rs) {
+      const int z = r / fs.y, y = r - z * fs.y;
+      src = s.seed_of(it.slot) +
+            ((size_t)(it.a0[0] + z) * s.canvas.y + it.a0[1] + y) * s.canvas.x +
+            it.a0[2];
+      dst = seed_out + blockIdx.y * fs.voxels() + (size_t)r * fs.x;
+      nx = fs.x;
+    } else if (r < rs + ri) {
+      const int q = r - rs;
+      const int z = q / fi.y, y = q - z * fi.y;
+      src = s.image_of(it.slot) +
+            ((size_t)(it.b0[0] + z) * s.image_patch.y + it.b0[1] + y) *
+                s.image_patch.x + it.b0[2];
+      dst = image_out + blockIdx.y * fi.voxels() + (size_t)q * fi.x;
+      nx = fi.x;
+    } else {
+      const int q = r - rs - ri;
+      const int z = q / pm.y, y = q - z * pm.y;
+      src = s.labels_of(it.slot) +
+            ((size_t)(it.c0[0] + z) * s.label_patch.y + it.c0[1] + y) *
+                s.label_patch.x + it.c0[2];
+      dst = labels_out + blockIdx.y * pm.voxels() + (size_t)q * pm.x;
+      nx = pm.x;
+    }
+    for (int x = lane; x < nx; x += 64) dst[x] = src[x];
   }
 }
 
@@ -367,10 +581,11 @@ struct ffn_evaluation : ffn_unit::Unit {
   bool configured = false;
   ffn_evaluation_geometry g;
   DevBuf seed, image, labels;  // slots x array
-  DevBuf io_seed, io_image, io_logits;
+  DevBuf io_seed, io_image, io_logits, io_labels;
   DevBuf items, results, partials;
   PinnedBuf stage;
   double ms[6] = {0, 0, 0, 0, 0, 0}, bytes[6] = {0, 0, 0, 0, 0, 0};
+  double ms_train[2] = {0, 0}, bytes_train[2] = {0, 0};
 
   SlotArrays arrays() const {
     SlotArrays s;
@@ -509,6 +724,8 @@ int ffn_evaluation_configure(ffn_evaluation* h,
   U_OK(ensure(h->io_seed, g.slots * fs * sizeof(float)));
   U_OK(ensure(h->io_image, g.slots * fi * sizeof(float)));
   U_OK(ensure(h->io_logits, g.slots * fs * sizeof(float)));
+  U_OK(ensure(h->io_labels,
+              g.slots * dims_of(g.pred_mask_zyx).voxels() * sizeof(float)));
   h->g = g;
   h->configured = true;
   return FFN_OK;
@@ -572,22 +789,28 @@ int ffn_evaluation_add_volume(ffn_evaluation* h, const void* image,
   return FFN_OK;
 }
 
-int ffn_evaluation_load(ffn_evaluation* h, int n, const int32_t* slots,
-                        const int32_t* volumes, const int32_t* centres_xyz,
-                        const float* offsets, const float* scales,
-                        float seed_pad_logit, float seed_centre_logit) {
+}  // extern "C"
+
+namespace {
+
+// The argument checks of load and the validated entries; items[k] is written
+// through `at(k)`, which load and load_augmented lay out differently.
+template <typename At>
+int load_items(ffn_evaluation* h, int n, const int32_t* slots,
+               const int32_t* volumes, const int32_t* centres_xyz,
+               const float* offsets, const float* scales, At at,
+               double* volume_bytes_out) {
   U_OK(ready(h));
   if (!slots || !volumes || !centres_xyz || !offsets || !scales)
     return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   U_OK(check_slots(h, n, slots, true));
   const ffn_evaluation_geometry& g = h->g;
-  LoadItem items[kMaxSlots];
   double volume_bytes = 0.0;
   for (int k = 0; k < n; ++k) {
     if (volumes[k] < 0 || (size_t)volumes[k] >= h->volumes.size())
       return ffn_set_error(FFN_ERR_ARG, "no volume %d", volumes[k]);
     const Volume& v = *h->volumes[volumes[k]];
-    LoadItem& it = items[k];
+    LoadItem& it = at(k);
     it.image = v.image.p;
     it.labels = v.labels.p;
     it.sy = v.shape[1] * v.shape[2];
@@ -613,6 +836,29 @@ int ffn_evaluation_load(ffn_evaluation* h, int n, const int32_t* slots,
     volume_bytes += (double)dims_of(g.image_patch_zyx).voxels() * v.image_elem +
                     (double)dims_of(g.label_patch_zyx).voxels() * v.label_elem;
   }
+  *volume_bytes_out = volume_bytes;
+  return FFN_OK;
+}
+
+double load_bytes(const SlotArrays& s, int n, double volume_bytes) {
+  return volume_bytes + 4.0 * n * (double)(s.image_patch.voxels() +
+                                           s.label_patch.voxels() +
+                                           s.canvas.voxels());
+}
+
+}  // namespace
+
+extern "C" {
+
+int ffn_evaluation_load(ffn_evaluation* h, int n, const int32_t* slots,
+                        const int32_t* volumes, const int32_t* centres_xyz,
+                        const float* offsets, const float* scales,
+                        float seed_pad_logit, float seed_centre_logit) {
+  LoadItem items[kMaxSlots];
+  double volume_bytes = 0.0;
+  U_OK(load_items(h, n, slots, volumes, centres_xyz, offsets, scales,
+                  [&](int k) -> LoadItem& { return items[k]; },
+                  &volume_bytes));
   U_OK(send_items(h, items, n * sizeof(LoadItem)));
   const SlotArrays s = h->arrays();
   const int rows = s.image_patch.z * s.image_patch.y +
@@ -625,9 +871,83 @@ int ffn_evaluation_load(ffn_evaluation* h, int n, const int32_t* slots,
   U_TRY(hipGetLastError());
   U_OK(h->timer_stop(&ms));
   h->ms[0] = ms;
-  h->bytes[0] = volume_bytes + 4.0 * n * (double)(s.image_patch.voxels() +
-                                                  s.label_patch.voxels() +
-                                                  s.canvas.voxels());
+  h->bytes[0] = load_bytes(s, n, volume_bytes);
+  return FFN_OK;
+}
+
+int ffn_evaluation_load_augmented(ffn_evaluation* h, int n,
+                                  const int32_t* slots, const int32_t* volumes,
+                                  const int32_t* centres_xyz,
+                                  const float* offsets, const float* scales,
+                                  const int32_t* perms, const uint8_t* reflects,
+                                  float seed_pad_logit,
+                                  float seed_centre_logit) {
+  AugItem items[kMaxSlots];
+  double volume_bytes = 0.0;
+  U_OK(load_items(h, n, slots, volumes, centres_xyz, offsets, scales,
+                  [&](int k) -> LoadItem& { return items[k].load; },
+                  &volume_bytes));
+  if (!perms || !reflects) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  const ffn_evaluation_geometry& g = h->g;
+  const SlotArrays s = h->arrays();
+  const int rc = s.canvas.z * s.canvas.y;
+  auto tiles = [](int n) { return (n + kTile - 1) / kTile; };
+  int blocks = 1;
+  for (int k = 0; k < n; ++k) {
+    const int32_t* perm = perms + 3 * k;
+    const uint8_t* ref = reflects + 3 * k;
+    unsigned seen = 0;
+    for (int a = 0; a < 3; ++a) {
+      if (perm[a] < 0 || perm[a] > 2 || ((seen >> perm[a]) & 1))
+        return ffn_set_error(FFN_ERR_ARG,
+                             "(%d, %d, %d) is not a permutation of 0, 1, 2",
+                             perm[0], perm[1], perm[2]);
+      seen |= 1u << perm[a];
+      if (ref[a] > 1)
+        return ffn_set_error(FFN_ERR_ARG, "reflect value %d is not 0 or 1",
+                             (int)ref[a]);
+    }
+    for (int a = 0; a < 3; ++a)
+      if (perm[a] != a &&
+          (g.image_patch_zyx[a] != g.image_patch_zyx[perm[a]] ||
+           g.label_patch_zyx[a] != g.label_patch_zyx[perm[a]]))
+        return ffn_set_error(FFN_ERR_ARG,
+                             "axes %d and %d change places but differ in patch "
+                             "size", a, perm[a]);
+    AugItem& it = items[k];
+    it.x_moves = perm[2] != 2;
+    it.a2 = it.p2 = it.swap = 0;
+    int units;
+    if (!it.x_moves) {
+      it.swap = perm[0] == 1;
+      it.ra = ref[0];
+      it.rb = ref[1];
+      units = (s.image_patch.z * s.image_patch.y +
+               s.label_patch.z * s.label_patch.y + rc + kWaves - 1) / kWaves;
+    } else {
+      it.a2 = perm[0] == 2 ? 0 : 1;
+      it.p2 = perm[2];
+      const int b = 1 - it.a2;
+      it.ra = ref[it.a2];
+      it.rb = ref[b];
+      units = (rc + kWaves - 1) / kWaves;
+      for (const int32_t* S : {g.image_patch_zyx, g.label_patch_zyx})
+        units += S[b] * tiles(S[it.a2]) * tiles(S[2]);
+    }
+    it.rx = ref[2];
+    if (units > blocks) blocks = units;
+  }
+  if (blocks > kRowBlocks) blocks = kRowBlocks;
+  U_OK(send_items(h, items, n * sizeof(AugItem)));
+  double ms = 0.0;
+  U_OK(h->timer_start());
+  hipLaunchKernelGGL(load_augmented_kernel, dim3(blocks, n), dim3(kThreads), 0,
+                     h->stream, static_cast<const AugItem*>(h->items.p), s,
+                     seed_pad_logit, seed_centre_logit);
+  U_TRY(hipGetLastError());
+  U_OK(h->timer_stop(&ms));
+  h->ms_train[0] = ms;
+  h->bytes_train[0] = load_bytes(s, n, volume_bytes);
   return FFN_OK;
 }
 
@@ -701,6 +1021,63 @@ int ffn_evaluation_gather(ffn_evaluation* h, int n, const int32_t* slots,
   U_OK(h->timer_stop(&ms));
   h->ms[2] = ms;
   h->bytes[2] = 8.0 * n * (double)(fs.voxels() + fi.voxels());
+  return FFN_OK;
+}
+
+int ffn_evaluation_gather_train(ffn_evaluation* h, int n, const int32_t* slots,
+                                const int32_t* offsets_xyz, float* seed_out_dev,
+                                float* image_out_dev, float* labels_out_dev) {
+  U_OK(ready(h));
+  if (!slots || !offsets_xyz || !seed_out_dev || !image_out_dev ||
+      !labels_out_dev)
+    return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  U_OK(check_slots(h, n, slots, false));
+  const ffn_evaluation_geometry& g = h->g;
+  TrainBoxItem items[kMaxSlots];
+  for (int k = 0; k < n; ++k) {
+    items[k].slot = slots[k];
+    U_OK(box_start(g.canvas_zyx, g.input_seed_zyx, offsets_xyz + 3 * k,
+                   items[k].a0, "input_seed"));
+    U_OK(box_start(g.image_patch_zyx, g.input_image_zyx, offsets_xyz + 3 * k,
+                   items[k].b0, "input_image"));
+    U_OK(box_start(g.label_patch_zyx, g.pred_mask_zyx, offsets_xyz + 3 * k,
+                   items[k].c0, "pred_mask"));
+  }
+  U_OK(send_items(h, items, n * sizeof(TrainBoxItem)));
+  const Dims fs = dims_of(g.input_seed_zyx), fi = dims_of(g.input_image_zyx),
+             pm = dims_of(g.pred_mask_zyx);
+  double ms = 0.0;
+  U_OK(h->timer_start());
+  hipLaunchKernelGGL(
+      gather_train_kernel,
+      dim3(row_blocks(fs.z * fs.y + fi.z * fi.y + pm.z * pm.y), n),
+      dim3(kThreads), 0, h->stream,
+      static_cast<const TrainBoxItem*>(h->items.p), h->arrays(), fs, fi, pm,
+      seed_out_dev, image_out_dev, labels_out_dev);
+  U_TRY(hipGetLastError());
+  U_OK(h->timer_stop(&ms));
+  h->ms_train[1] = ms;
+  h->bytes_train[1] =
+      8.0 * n * (double)(fs.voxels() + fi.voxels() + pm.voxels());
+  return FFN_OK;
+}
+
+int ffn_evaluation_io_labels(ffn_evaluation* h, float** labels_dev) {
+  if (!h || !labels_dev) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  if (!h->configured)
+    return ffn_set_error(FFN_ERR_STATE, "ffn_evaluation_configure not called");
+  *labels_dev = static_cast<float*>(h->io_labels.p);
+  return FFN_OK;
+}
+
+int ffn_evaluation_last_timing_train(ffn_evaluation* h, double kernel_ms[2],
+                                     double algorithmic_bytes[2]) {
+  if (!h || !kernel_ms || !algorithmic_bytes)
+    return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  for (int k = 0; k < 2; ++k) {
+    kernel_ms[k] = h->ms_train[k];
+    algorithmic_bytes[k] = h->bytes_train[k];
+  }
   return FFN_OK;
 }
 

@@ -13,10 +13,14 @@ queue and the `done` set.  `EvalResult` holds the accumulators of the
 reference's EvalTracker and `summaries()` its scalar summaries under the same
 tags.  No CPU fallback: without the library / a GPU every device call raises.
 
-Not covered: any backward pass, the augmentations of train.py
-(evaluation runs unaugmented, so every loss weight is 1), the
-`fixed_offsets_window` policy, image and mesh summaries, weighted or sampled
-coordinate sources.
+Not covered: any backward pass, augmentation (evaluation runs
+unaugmented; every loss weight is 1), the `fixed_offsets_window` policy, image
+and mesh summaries, weighted or sampled coordinate sources.
+
+For training the unit also has `load_augmented` (load with
+train.py's PermuteAndReflect) and `gather_train` (gather plus the labels of the
+FoV); `FovWalk` holds the host halves of the move policies for this module's
+CheckpointEvaluator and for examples.BatchExampleIter.
 """
 
 from __future__ import annotations
@@ -41,6 +45,7 @@ MAX_SLOTS = 32
 #: EvalTracker.eval_threshold (tracker.py:87)
 EVAL_PROBABILITY = 0.9
 CALL_KINDS = ('load', 'probe_moves', 'gather', 'paste', 'score_faces', 'finish')
+TRAIN_CALL_KINDS = ('load_augmented', 'gather_train')
 
 
 def logit(p) -> float:
@@ -209,6 +214,35 @@ class EvaluationOps(_unit.Handle):
           centres.ctypes.data, offsets.ctypes.data, scales.ctypes.data,
           float(f32_logit(seed_pad)), float(f32_logit(0.95))))
 
+  def load_augmented(self, slots, volumes, centres_xyz, offsets, scales,
+                     perms, reflects, seed_pad: float):
+    """load() followed by train.py's PermuteAndReflect on the image and label
+    patches: `perms` (n, 3) holds the source axis of each output axis in zyx
+    numbering (np.transpose), `reflects` (n, 3) 0 / 1 per output axis.  The
+    seed canvas is not transformed.  Raises, touching no slot, on what load()
+    refuses, on a perm that is no permutation, and on axes of different patch
+    sizes changing places."""
+    slots = _i32(slots)
+    volumes = _i32(volumes)
+    centres = _i32(centres_xyz, (-1, 3))
+    offsets = np.ascontiguousarray(offsets, dtype=np.float32)
+    scales = np.ascontiguousarray(scales, dtype=np.float32)
+    perms = _i32(perms, (-1, 3))
+    reflects_in = np.asarray(reflects).reshape(-1, 3)
+    if ((reflects_in < 0) | (reflects_in > 255)).any():  # the library sees u8
+      raise ValueError('a reflect value is 0 or 1')
+    reflects = np.ascontiguousarray(reflects_in, dtype=np.uint8)
+    if not (len(slots) == len(volumes) == len(centres) == len(offsets) ==
+            len(scales) == len(perms) == len(reflects)):
+      raise ValueError('one volume, centre, offset, scale, perm and reflect '
+                       'per slot')
+    with self.lock:
+      check(self._lib.ffn_evaluation_load_augmented(
+          self._h, len(slots), slots.ctypes.data, volumes.ctypes.data,
+          centres.ctypes.data, offsets.ctypes.data, scales.ctypes.data,
+          perms.ctypes.data, reflects.ctypes.data,
+          float(f32_logit(seed_pad)), float(f32_logit(0.95))))
+
   def probe_moves(self, slots, offsets_xyz, seed_threshold: float,
                   label_threshold: float):
     """(valid, wanted) bool arrays, one entry per (slot, offset) pair.  The
@@ -251,6 +285,26 @@ class EvaluationOps(_unit.Handle):
       check(self._lib.ffn_evaluation_gather(
           self._h, len(slots), slots.ctypes.data, offsets.ctypes.data,
           _address(seed_out), _address(image_out)))
+
+  def alloc_io_train(self, n: int):
+    """alloc_io()'s three arrays and a fourth for the labels of gather_train:
+    [n, pred_mask]."""
+    seed, image, logits = self.alloc_io(n)
+    ptr = ctypes.c_void_p()
+    with self.lock:
+      check(self._lib.ffn_evaluation_io_labels(self._h, ctypes.byref(ptr)))
+    return seed, image, logits, DeviceArray(ptr.value,
+                                            (n,) + self.geometry.pred_mask)
+
+  def gather_train(self, slots, offsets_xyz, seed_out, image_out, labels_out):
+    """gather(), and the pred_mask crop of every entry's soft labels at its
+    offset (examples.py:65) into the device array `labels_out`."""
+    slots = _i32(slots)
+    offsets = _i32(offsets_xyz, (-1, 3))
+    with self.lock:
+      check(self._lib.ffn_evaluation_gather_train(
+          self._h, len(slots), slots.ctypes.data, offsets.ctypes.data,
+          _address(seed_out), _address(image_out), _address(labels_out)))
 
   def paste(self, slots, offsets_xyz, logits, layout: int = LOGITS_PRED):
     """BatchExampleIter.update_seeds from the device array `logits`: dense
@@ -322,6 +376,14 @@ class EvaluationOps(_unit.Handle):
     nbytes = (ctypes.c_double * 6)()
     check(self._lib.ffn_evaluation_last_timing(self._h, ms, nbytes))
     return {kind: (ms[k], nbytes[k]) for k, kind in enumerate(CALL_KINDS)}
+
+  def last_timing_train(self) -> Dict[str, Tuple[float, float]]:
+    """last_timing() of the last load_augmented and gather_train."""
+    ms = (ctypes.c_double * 2)()
+    nbytes = (ctypes.c_double * 2)()
+    check(self._lib.ffn_evaluation_last_timing_train(self._h, ms, nbytes))
+    return {kind: (ms[k], nbytes[k])
+            for k, kind in enumerate(TRAIN_CALL_KINDS)}
 
 
 def _address(array) -> int:
@@ -451,6 +513,107 @@ class _Stream:
     self.offset = None    # offset of the step being made
 
 
+class FovWalk:
+  """The host halves of the move policies of train.py:359-373
+  (examples.fixed_offsets, max_pred_offsets, no_offsets): which offsets a
+  stream may ask the device about, which one it takes next, and what it queues
+  after a step.  Shared by CheckpointEvaluator and examples.BatchExampleIter.
+
+  `result` arguments are anything with EvalResult.record_move."""
+
+  def __init__(self, fov_policy: str, geometry: Geometry, shifts, deltas_xyz,
+               threshold: float):
+    if fov_policy not in POLICIES:
+      raise ValueError('fov_policy is one of %r, got %r' %
+                       (POLICIES, fov_policy))
+    self.fov_policy = fov_policy
+    self.shifts = [tuple(int(v) for v in s) for s in shifts]
+    self.deltas_xyz = tuple(int(v) for v in deltas_xyz)
+    self.deltas_zyx = tuple(geometry.deltas)
+    self.max_radius = geometry.max_radius_xyz()
+    self.threshold = float(threshold)  # of the seed, in logits
+
+  @staticmethod
+  def new_stream() -> _Stream:
+    """The host state of one slot, idle."""
+    return _Stream()
+
+  def start(self, stream: _Stream, example: int):
+    stream.example = example
+    stream.offset = None
+    if self.fov_policy == 'fixed':
+      stream.pending = [(0, 0, 0)] + self.shifts
+    elif self.fov_policy == 'max_pred_moves':
+      stream.pending = collections.deque([(0, 0, 0)])
+      stream.done = set()
+    else:
+      stream.pending = [(0, 0, 0)]
+
+  def quantize(self, offset):
+    d = self.deltas_xyz
+    return tuple((o + dd / 2) // max(dd, 1) for o, dd in zip(offset, d))
+
+  def candidates(self, stream: _Stream):
+    """The pending offsets whose seed and label values the next walk may ask
+    for: the seed does not change before the stream's next step."""
+    if self.fov_policy == 'fixed':
+      return list(stream.pending)
+    if self.fov_policy == 'max_pred_moves':
+      return [o for o in stream.pending
+              if not any(abs(v) > m for v, m in zip(o, self.max_radius))]
+    return []
+
+  def next_offset(self, stream: _Stream, probed, result: EvalResult, records):
+    """Walks the pending offsets as the policy's generator does until one is to
+    be taken; returns it, or None when the example is exhausted."""
+    if self.fov_policy == 'no_step':
+      if not stream.pending:
+        return None
+      stream.pending = []
+      result.record_move(True, True, (0, 0, 0))
+      records.append((True, True, (0, 0, 0)))
+      return (0, 0, 0)
+    if self.fov_policy == 'fixed':
+      while stream.pending:
+        off = stream.pending.pop(0)
+        valid, wanted = probed[off]
+        result.record_move(wanted, valid, off)
+        records.append((wanted, valid, off))
+        if valid:
+          return off
+      return None
+    while stream.pending:
+      off = stream.pending.popleft()
+      if any(abs(v) > m for v, m in zip(off, self.max_radius)):
+        continue
+      quantized = self.quantize(off)
+      if quantized in stream.done:
+        continue
+      valid, wanted = probed[off]
+      result.record_move(wanted, valid, (0, 0, 0))
+      records.append((wanted, valid, (0, 0, 0)))
+      if not valid or (not wanted and quantized != (0, 0, 0)):
+        continue
+      stream.done.add(quantized)
+      return off
+    return None
+
+  def extend_queue(self, stream: _Stream, scores, positions):
+    """max_pred_offsets' tail: the face maxima at or above the threshold,
+    highest first, queued relative to the step's offset."""
+    found = set()
+    for f in range(6):
+      if self.deltas_zyx[f // 2] == 0:
+        continue
+      score = scores[f]
+      if score < ceil_f32(self.threshold):
+        continue
+      found.add((float(score), tuple(int(v) for v in positions[f])))
+    off = stream.offset
+    for _, p in sorted(found, reverse=True):
+      stream.pending.append((p[2] + off[0], p[1] + off[1], p[0] + off[2]))
+
+
 class CheckpointEvaluator:
   """Scores a checkpoint on a finite list of training coordinates.
 
@@ -497,6 +660,8 @@ class CheckpointEvaluator:
       random.Random(shuffle_seed).shuffle(self.shifts)
     self.deltas_xyz = tuple(int(v) for v in np.asarray(model.info.deltas))
     self.max_radius = self.geometry.max_radius_xyz()
+    self.walk = FovWalk(fov_policy, self.geometry, self.shifts,
+                        self.deltas_xyz, self.threshold)
     self._volumes = {}
     ops.configure(self.geometry)
     ops.reset()  # the unit serves one evaluator at a time
@@ -529,83 +694,6 @@ class CheckpointEvaluator:
           return False
     return True
 
-  # -- the move policies: host halves ------------------------------------------------
-
-  def _start(self, stream: _Stream, example: int):
-    stream.example = example
-    stream.offset = None
-    if self.fov_policy == 'fixed':
-      stream.pending = [(0, 0, 0)] + self.shifts
-    elif self.fov_policy == 'max_pred_moves':
-      stream.pending = collections.deque([(0, 0, 0)])
-      stream.done = set()
-    else:
-      stream.pending = [(0, 0, 0)]
-
-  def _quantize(self, offset):
-    d = self.deltas_xyz
-    return tuple((o + dd / 2) // max(dd, 1) for o, dd in zip(offset, d))
-
-  def _candidates(self, stream: _Stream):
-    """The pending offsets whose seed and label values the next walk may ask
-    for: the seed does not change before the stream's next step."""
-    if self.fov_policy == 'fixed':
-      return list(stream.pending)
-    if self.fov_policy == 'max_pred_moves':
-      return [o for o in stream.pending
-              if not any(abs(v) > m for v, m in zip(o, self.max_radius))]
-    return []
-
-  def _next_offset(self, stream: _Stream, probed, result: EvalResult, records):
-    """Walks the pending offsets as the policy's generator does until one is to
-    be taken; returns it, or None when the example is exhausted."""
-    if self.fov_policy == 'no_step':
-      if not stream.pending:
-        return None
-      stream.pending = []
-      result.record_move(True, True, (0, 0, 0))
-      records.append((True, True, (0, 0, 0)))
-      return (0, 0, 0)
-    if self.fov_policy == 'fixed':
-      while stream.pending:
-        off = stream.pending.pop(0)
-        valid, wanted = probed[off]
-        result.record_move(wanted, valid, off)
-        records.append((wanted, valid, off))
-        if valid:
-          return off
-      return None
-    while stream.pending:
-      off = stream.pending.popleft()
-      if any(abs(v) > m for v, m in zip(off, self.max_radius)):
-        continue
-      quantized = self._quantize(off)
-      if quantized in stream.done:
-        continue
-      valid, wanted = probed[off]
-      result.record_move(wanted, valid, (0, 0, 0))
-      records.append((wanted, valid, (0, 0, 0)))
-      if not valid or (not wanted and quantized != (0, 0, 0)):
-        continue
-      stream.done.add(quantized)
-      return off
-    return None
-
-  def _extend_queue(self, stream: _Stream, scores, positions):
-    """max_pred_offsets' tail: the face maxima at or above the threshold,
-    highest first, queued relative to the step's offset."""
-    found = set()
-    for f in range(6):
-      if self.geometry.deltas[f // 2] == 0:
-        continue
-      score = scores[f]
-      if score < ceil_f32(self.threshold):
-        continue
-      found.add((float(score), tuple(int(v) for v in positions[f])))
-    off = stream.offset
-    for _, p in sorted(found, reverse=True):
-      stream.pending.append((p[2] + off[0], p[1] + off[1], p[0] + off[2]))
-
   # -- the loop ----------------------------------------------------------------------
 
   def evaluate(self, coordinates, max_examples: Optional[int] = None
@@ -626,7 +714,7 @@ class CheckpointEvaluator:
         break
     result.offsets = [[] for _ in todo]
     result.records = [[] for _ in todo]
-    streams = [_Stream() for _ in range(self.batch_size)]
+    streams = [self.walk.new_stream() for _ in range(self.batch_size)]
     next_example = 0
     eval_voxels = int(np.prod(self.geometry.eval))
     pred_voxels = int(np.prod(self.geometry.pred_mask))
@@ -639,7 +727,7 @@ class CheckpointEvaluator:
         fresh = []
         for s in need:
           if streams[s].example is None and next_example < len(todo):
-            self._start(streams[s], next_example)
+            self.walk.start(streams[s], next_example)
             fresh.append(s)
             next_example += 1
         if fresh:
@@ -649,7 +737,7 @@ class CheckpointEvaluator:
                         [v[2] for v in vols], [v[3] for v in vols],
                         self.seed_pad)
         need = [s for s in need if streams[s].example is not None]
-        pairs = [(s, o) for s in need for o in self._candidates(streams[s])]
+        pairs = [(s, o) for s in need for o in self.walk.candidates(streams[s])]
         probed = {s: {} for s in need}
         if pairs:
           valid, wanted = self.ops.probe_moves(
@@ -660,8 +748,8 @@ class CheckpointEvaluator:
         again = []
         for s in need:
           stream = streams[s]
-          stream.offset = self._next_offset(stream, probed[s], result,
-                                            result.records[stream.example])
+          stream.offset = self.walk.next_offset(stream, probed[s], result,
+                                                result.records[stream.example])
           if stream.offset is None:
             loss_sum, counts, masked = self.ops.finish(s)
             result.add_patch(loss_sum / eval_voxels, counts, eval_voxels,
@@ -688,6 +776,6 @@ class CheckpointEvaluator:
       if self.fov_policy == 'max_pred_moves':
         scores, positions = self.ops.score_faces(active, offsets)
         for k, s in enumerate(active):
-          self._extend_queue(streams[s], scores[k], positions[k])
+          self.walk.extend_queue(streams[s], scores[k], positions[k])
     self.total_seconds += time.time() - t_begin
     return result

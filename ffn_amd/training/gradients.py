@@ -131,8 +131,10 @@ class ConvStackGradients:
     if not 1 <= int(max_batch) <= MAX_BATCH:
       raise ValueError('max_batch = %r, expected 1 .. %d' %
                        (max_batch, MAX_BATCH))
-    self.ops = GradientOps(device_id)  # raises without a GPU
+    # (before the library is loaded: torch brings its own copy of the HIP
+    # runtime, and the process must end up with one)
     import torch  # pylint:disable=g-import-not-at-top
+    self.ops = GradientOps(device_id)  # raises without a GPU
     self.torch = torch
     self.device = torch.device('cuda', device_id)
     self.depth = int(model.depth)

@@ -10,9 +10,9 @@ learning-rate decay, and the step counter.
 The variables, their gradients and the optimizer's slots each live in one flat
 device array (optimizer.arena_layout); the gradient kernels read and write
 views into these arrays and the update is one launch over all of them.  No
-gradient or parameter crosses to the host in a step.  The example iterator,
-augmentation and checkpoint writing of a train.py are not here, and there is no
-CPU fallback: without a GPU the constructor raises.
+gradient or parameter crosses to the host in a step.  The example iterator is
+training/examples.py, the loop and the checkpoint files are train.py's.  There
+is no CPU fallback: without a GPU the constructor raises.
 """
 
 from __future__ import annotations
@@ -41,10 +41,12 @@ class ConvStackTrainer:
     if model.variables is None:
       raise ValueError('model has no weights (load_checkpoint / init_random)')
     self.config = config
+    # (before the library is loaded: torch brings its own copy of the HIP
+    # runtime, and the process must end up with one)
+    import torch  # pylint:disable=g-import-not-at-top
     self.ops = optimizer_lib.OptimizerOps(device_id)  # raises without a GPU
     self.csg = None
     try:
-      import torch  # pylint:disable=g-import-not-at-top
       self.torch = torch
       self.device = torch.device('cuda', device_id)
       self.layout = optimizer_lib.arena_layout(model.depth, model.features)
@@ -83,12 +85,19 @@ class ConvStackTrainer:
 
   # -- the step ------------------------------------------------------------------
   def train_step(self, seed, image, labels, weights):
+    """train_step_device with the updated seed as numpy [n, z, y, x]."""
+    loss, logits_dev, step = self.train_step_device(seed, image, labels,
+                                                    weights)
+    return loss, logits_dev.cpu().numpy(), step
+
+  def train_step_device(self, seed, image, labels, weights):
     """seed, image, labels, weights: [n, z, y, x], numpy or device arrays.
 
     Returns (loss, logits, step): the loss of the batch under the variables
-    before the update, the updated seed as numpy [n, z, y, x], and the step
-    counter after the update.  Raises InvalidLossError, having changed nothing,
-    if the loss or a gradient entry is not finite."""
+    before the update, the updated seed [n, z, y, x] as a device tensor that is
+    valid until the next step, and the step counter after the update.  Raises
+    InvalidLossError, having changed nothing, if the loss or a gradient entry
+    is not finite."""
     cfg, total = self.config, self.layout.total
     loss, logits_dev = self.csg.loss_and_gradients_device(seed, image, labels,
                                                           weights)
@@ -114,7 +123,7 @@ class ConvStackTrainer:
     if cfg.optimizer == 'adam':
       self.beta1_power, self.beta2_power = cfg.advance_powers(
           self.beta1_power, self.beta2_power)
-    return loss, logits_dev.cpu().numpy(), self.global_step
+    return loss, logits_dev, self.global_step
 
   # -- state ---------------------------------------------------------------------
   def _download(self, arena):

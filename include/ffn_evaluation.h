@@ -169,6 +169,45 @@ int ffn_evaluation_write_seed(ffn_evaluation* h, int slot, const float* in);
 int ffn_evaluation_last_timing(ffn_evaluation* h, double kernel_ms[6],
                                double algorithmic_bytes[6]);
 
+/* ---- what a training loop needs on top of the above (train.py:252-274) ----
+ *
+ * load_augmented is load followed by train.py's PermuteAndReflect on the image
+ * and the label patch.  perms holds 3 int32 per entry: the source axis of each
+ * output axis in zyx numbering (np.transpose); reflects 3 uint8 per entry, 0 or
+ * 1.  With P the array load writes, the slot holds flip(transpose(P, perm),
+ * axes with reflect = 1): out[i] = P[k] with j_a = reflect[a] ? S_a - 1 - i_a :
+ * i_a and k[perm[a]] = j_a.  The box, the normalisation and the local object
+ * mask (against the label at the centre index of the untransformed patch) are
+ * load's; the seed canvas is load's fresh one, untransformed.  The identity
+ * writes what load writes, bit for bit.  FFN_ERR_ARG with no slot touched: a
+ * perm that is no permutation of 0, 1, 2; a reflect that is not 0 or 1; an axis
+ * a with perm[a] != a whose image-patch or label-patch size differs from that
+ * of axis perm[a]; any of load's own errors.  One launch. */
+int ffn_evaluation_load_augmented(ffn_evaluation* h, int n,
+                                  const int32_t* slots, const int32_t* volumes,
+                                  const int32_t* centres_xyz,
+                                  const float* offsets, const float* scales,
+                                  const int32_t* perms, const uint8_t* reflects,
+                                  float seed_pad_logit,
+                                  float seed_centre_logit);
+
+/* gather, and into labels_out_dev [n][pred_mask] the pred_mask box of the
+ * label patch at the offset (it starts at label_patch / 2 - pred_mask / 2 +
+ * offset per axis; examples.py:65), in one launch.  A box that leaves its
+ * array is FFN_ERR_ARG; nothing is written then. */
+int ffn_evaluation_gather_train(ffn_evaluation* h, int n, const int32_t* slots,
+                                const int32_t* offsets_xyz, float* seed_out_dev,
+                                float* image_out_dev, float* labels_out_dev);
+
+/* A fourth device array beside those of ffn_evaluation_io_buffers, with their
+ * lifetime: labels [slots][pred_mask], the third output of gather_train. */
+int ffn_evaluation_io_labels(ffn_evaluation* h, float** labels_dev);
+
+/* As last_timing, of the last load_augmented (index 0; bytes as load) and
+ * gather_train (1; every f32 once in and once out). */
+int ffn_evaluation_last_timing_train(ffn_evaluation* h, double kernel_ms[2],
+                                     double algorithmic_bytes[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,326 @@
+#!/usr/bin/env python3
+r"""Trains a ConvStack3DFFNModel on one MI355X: the reference's train.py with
+every voxel array resident on the GPU.
+
+  python train.py --train_coords tf_record_file \
+      --data_volumes validation1:grayscale.npy \
+      --label_volumes validation1:groundtruth.npy \
+      --model_name convstack_3d.ConvStack3DFFNModel \
+      --model_args '{"depth": 12, "fov_size": [33, 33, 33], "deltas": [8, 8, 8]}' \
+      --image_mean 128 --image_stddev 33 --train_dir /tmp/ffn_run
+
+The flags it shares with the reference mean what they mean there.  Volumes are
+given as evaluate_checkpoint.py takes them (`<name>:<file>.npy`,
+`<name>:<file>.npz:<array>`, or `<name>:<file>:<dataset>` of an HDF5 file where
+h5py is installed); coordinates come from a TFRecord file as
+build_coordinates.py writes it.  The loop is the reference's: next batch ->
+train step -> update_seeds, with the examples, their augmentation and the FoV
+moves in ffn_amd/training/examples.py and the step in
+ffn_amd/training/trainer.py.  There is no CPU fallback: without a GPU the
+script raises.
+
+Every --checkpoint_steps steps and at the end two files are written to
+--train_dir:
+
+  model.ckpt-<step>.npz        the variables under their TensorFlow names;
+                               evaluate_checkpoint.py --checkpoint takes it
+  model.ckpt-<step>.state.npz  the rest of ConvStackTrainer.state(): optimizer
+                               slots, step counter, adam's beta powers, flags
+
+A run resumes from the newest pair found in --train_dir (its example streams
+start afresh, as the reference's do).  Summaries are appended to
+<train_dir>/summaries.jsonl as JSON lines every --summary_rate_secs seconds:
+step, loss, learning rate, clipped gradient entries and the tracker's eval/*
+and moves/* summaries, which are then reset (train.py:422-423).  A loss or a
+gradient that is not finite ends the run with InvalidLossError; the last
+checkpoint written stays as it is.
+
+Not here: TensorFlow-format checkpoints, replicas (--master, --task,
+--ps_tasks, --replica_step_delay), tf.train.shuffle_batch's queue (the
+coordinates are cycled, reshuffled per epoch), image summaries.  TensorFlow's
+random number streams are not reproduced: --seed makes a run of this script
+reproducible.
+"""
+
+import argparse
+import json
+import logging
+import os
+import re
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+
+import evaluate_checkpoint as volumes_lib  # noqa: E402  (volume, map helpers)
+from ffn_amd import coordinates as coordinate_ops  # noqa: E402
+from ffn_amd.training import augmentation  # noqa: E402
+from ffn_amd.training import evaluation  # noqa: E402
+from ffn_amd.training import examples  # noqa: E402
+from ffn_amd.training import optimizer as optimizer_lib  # noqa: E402
+from ffn_amd.training.import_util import import_symbol  # noqa: E402
+
+CHECKPOINT_RE = re.compile(r'^model\.ckpt-(\d+)\.npz$')
+
+
+def _csv(text):
+  return [v for v in text.split(',') if v.strip()]
+
+
+def _axes(text):
+  return [int(v) for v in _csv(text)]
+
+
+def _boolean(text):
+  if text.lower() in ('true', '1', 'yes'):
+    return True
+  if text.lower() in ('false', '0', 'no'):
+    return False
+  raise argparse.ArgumentTypeError('expected true or false, got %r' % text)
+
+
+def parse_args(argv=None):
+  ap = argparse.ArgumentParser(
+      description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+  # training data (train.py:50-72)
+  ap.add_argument('--train_coords', required=True,
+                  help='TFRecord file of coordinates (GZIP or plain)')
+  ap.add_argument('--data_volumes', required=True, type=_csv,
+                  help='comma-separated image volumes, <name>:<file>...')
+  ap.add_argument('--label_volumes', required=True, type=_csv,
+                  help='comma-separated label volumes under the same names')
+  ap.add_argument('--model_name', required=True)
+  ap.add_argument('--model_args', required=True, type=json.loads,
+                  help='JSON arguments of the model class')
+  # training infra (train.py:75-88)
+  ap.add_argument('--train_dir', default='/tmp')
+  ap.add_argument('--batch_size', type=int, default=4)
+  ap.add_argument('--max_steps', type=int, default=10000)
+  ap.add_argument('--summary_rate_secs', type=int, default=120)
+  # FFN training options (train.py:91-130)
+  ap.add_argument('--seed_pad', type=float, default=0.05)
+  ap.add_argument('--threshold', type=float, default=0.9)
+  ap.add_argument('--fov_policy', default='fixed',
+                  choices=examples.TRAIN_POLICIES)
+  ap.add_argument('--fov_moves', type=int, default=1)
+  ap.add_argument('--shuffle_moves', type=_boolean, nargs='?', const=True,
+                  default=True)
+  ap.add_argument('--image_mean', type=float, default=None)
+  ap.add_argument('--image_stddev', type=float, default=None)
+  ap.add_argument('--image_offset_scale_map', type=_csv, default=None)
+  ap.add_argument('--permutable_axes', type=_axes, default=[1, 2],
+                  help='subset of 0,1,2: the z, y, x axes that may change '
+                  'places')
+  ap.add_argument('--reflectable_axes', type=_axes, default=[0, 1, 2],
+                  help='subset of 0,1,2: the z, y, x axes that may be reversed')
+  # the optimizer's flags (ffn/training/optimizer.py)
+  defaults = optimizer_lib.OptimizerConfig()
+  ap.add_argument('--optimizer', default=defaults.optimizer,
+                  choices=optimizer_lib.RULES)
+  for name in optimizer_lib.OptimizerConfig.FIELDS[1:]:
+    kind = int if name == 'decay_steps' else float
+    ap.add_argument('--' + name, type=kind, default=getattr(defaults, name))
+  # this script's own
+  ap.add_argument('--seed', type=int, default=None,
+                  help='seeds the initial weights, the order of moves and '
+                  'coordinates, and the augmentation (default: the clock, as '
+                  'train.py:437)')
+  ap.add_argument('--checkpoint_steps', type=int, default=1000)
+  ap.add_argument('--device', type=int, default=0)
+  args = ap.parse_args(argv)
+  if ((args.image_stddev is None or args.image_mean is None) and
+      not args.image_offset_scale_map):
+    ap.error('--image_mean, --image_stddev or --image_offset_scale_map need to '
+             'be defined')
+  if not 1 <= args.batch_size <= evaluation.MAX_SLOTS:
+    ap.error('--batch_size must be in [1, %d]' % evaluation.MAX_SLOTS)
+  if args.checkpoint_steps < 1:
+    ap.error('--checkpoint_steps must be at least 1')
+  return args
+
+
+def optimizer_config(args):
+  return optimizer_lib.OptimizerConfig(
+      **{k: getattr(args, k) for k in optimizer_lib.OptimizerConfig.FIELDS})
+
+
+# ---- checkpoints -------------------------------------------------------------------
+
+
+def checkpoint_paths(train_dir, step):
+  prefix = os.path.join(train_dir, 'model.ckpt-%d' % step)
+  return prefix + '.npz', prefix + '.state.npz'
+
+
+def _savez(path, arrays):
+  tmp = path + '.tmp'
+  with open(tmp, 'wb') as f:
+    np.savez(f, **arrays)
+  os.replace(tmp, path)
+
+
+def save_checkpoint(train_dir, state):
+  """Writes the pair of files of a ConvStackTrainer.state(); returns their
+  paths.  The state file goes first: a pair is complete once the variables
+  exist."""
+  os.makedirs(train_dir, exist_ok=True)
+  variables_path, state_path = checkpoint_paths(train_dir,
+                                                int(state['global_step']))
+  rest = {'global_step': np.int64(state['global_step']),
+          'beta1_power': np.float32(state['beta1_power']),
+          'beta2_power': np.float32(state['beta2_power']),
+          'config': np.array(json.dumps(state['config'], sort_keys=True)),
+          'num_slots': np.int64(len(state['slots']))}
+  for k, slot in enumerate(state['slots']):
+    for name, value in slot.items():
+      rest['slot%d/%s' % (k, name)] = np.asarray(value, np.float32)
+  _savez(state_path, rest)
+  _savez(variables_path, {k: np.asarray(v, np.float32)
+                          for k, v in state['variables'].items()})
+  return variables_path, state_path
+
+
+def load_checkpoint(variables_path, state_path):
+  """-> a state as ConvStackTrainer.load_state takes it."""
+  with np.load(variables_path) as d:
+    variables = {k: d[k] for k in d.files}
+  with np.load(state_path) as d:
+    slots = [{} for _ in range(int(d['num_slots']))]
+    for key in d.files:
+      if key.startswith('slot'):
+        k, name = key.split('/', 1)
+        slots[int(k[4:])][name] = d[key]
+    return {'variables': variables, 'slots': slots,
+            'global_step': int(d['global_step']),
+            'beta1_power': np.float32(d['beta1_power']),
+            'beta2_power': np.float32(d['beta2_power']),
+            'config': json.loads(str(d['config']))}
+
+
+def newest_checkpoint(train_dir):
+  """(step, variables path, state path) of the complete pair with the largest
+  step in train_dir, or None."""
+  if not os.path.isdir(train_dir):
+    return None
+  best = None
+  for name in os.listdir(train_dir):
+    m = CHECKPOINT_RE.match(name)
+    if not m:
+      continue
+    step = int(m.group(1))
+    paths = checkpoint_paths(train_dir, step)
+    if os.path.exists(paths[1]) and (best is None or step > best[0]):
+      best = (step,) + paths
+  return best
+
+
+# ---- the run -----------------------------------------------------------------------
+
+
+def load_volumes(args):
+  """-> {name: (image, labels, offset, scale)}."""
+  images = dict(volumes_lib.load_volume(spec) for spec in args.data_volumes)
+  labels = dict(volumes_lib.load_volume(spec) for spec in args.label_volumes)
+  if set(images) != set(labels):
+    raise ValueError('image volumes %r and label volumes %r differ' %
+                     (sorted(images), sorted(labels)))
+  scales = volumes_lib.offset_scale_map(args.image_offset_scale_map)
+  out = {}
+  for name in sorted(images):
+    offset, scale = scales.get(name, (args.image_mean, args.image_stddev))
+    if offset is None or scale is None:
+      raise ValueError('no offset and scale for volume %r' % name)
+    out[name] = (images[name], labels[name], offset, scale)
+  return out
+
+
+def make_trainer(model, config, args):
+  """The device half: raises without a GPU (there is no other path)."""
+  from ffn_amd.training import trainer as trainer_lib  # pylint:disable=g-import-not-at-top
+  return trainer_lib.ConvStackTrainer(model, config, max_batch=args.batch_size,
+                                      device_id=args.device)
+
+
+def write_summary(f, trainer, batches, seconds):
+  stats = trainer.last_stats or {}
+  line = {'step': int(trainer.global_step), 'loss': stats.get('loss'),
+          'learning_rate': stats.get('learning_rate'),
+          'clipped': stats.get('clipped'), 'seconds': seconds,
+          'examples_finished': batches.examples_finished,
+          'epochs': batches.epochs}
+  line.update(batches.result.summaries())
+  batches.reset_result()
+  f.write(json.dumps({k: (float(v) if isinstance(v, np.floating) else v)
+                      for k, v in line.items()}, sort_keys=True) + '\n')
+  f.flush()
+
+
+def main(argv=None):
+  args = parse_args(argv)
+  logging.basicConfig(level=logging.INFO)
+  seed = int(time.time()) if args.seed is None else args.seed
+  logging.info('Random seed: %r', seed)
+  volumes = load_volumes(args)
+  centres, names = coordinate_ops.read_tfrecord(args.train_coords)
+  model = import_symbol(args.model_name)(batch_size=args.batch_size,
+                                         **args.model_args)
+  config = optimizer_config(args)
+  resume = newest_checkpoint(args.train_dir)
+  if resume is None:
+    model.init_random(seed=seed % (1 << 32))
+  else:
+    model.load_checkpoint(resume[1])
+  trainer = make_trainer(model, config, args)
+  try:
+    if resume is not None:
+      trainer.load_state(load_checkpoint(resume[1], resume[2]))
+      logging.info('Resumed from %s at step %d', resume[1],
+                   trainer.global_step)
+    transform = augmentation.PermuteAndReflect(
+        args.permutable_axes, args.reflectable_axes,
+        np.random.default_rng(seed))
+    ops = evaluation.default_ops(args.device)
+    geometry = evaluation.Geometry.from_info(model.info, args.fov_policy,
+                                             args.fov_moves, args.batch_size)
+    batches = examples.BatchExampleIter(
+        model.info, ops, volumes, zip(centres.tolist(), names),
+        fov_policy=args.fov_policy, fov_moves=args.fov_moves,
+        batch_size=args.batch_size, threshold=args.threshold,
+        seed_pad=args.seed_pad, shifts=model.shifts,
+        shuffle_moves=args.shuffle_moves, moves_seed=seed, transform=transform,
+        shuffle_seed=seed,
+        io=examples.torch_io(geometry, args.batch_size, trainer.device))
+    if batches.skipped:
+      logging.info('%d coordinates skipped (patch leaves the volume)',
+                   batches.skipped)
+    os.makedirs(args.train_dir, exist_ok=True)
+    saved = trainer.global_step if resume is not None else None
+    t_begin = t_last = time.time()
+    with open(os.path.join(args.train_dir, 'summaries.jsonl'), 'a') as summ:
+      while trainer.global_step < args.max_steps:
+        seed_io, image, labels, weights = batches.next()
+        _, logits, step = trainer.train_step_device(seed_io, image, labels,
+                                                    weights)
+        batches.update_seeds(logits)
+        now = time.time()
+        if now - t_last > args.summary_rate_secs:
+          write_summary(summ, trainer, batches, now - t_begin)
+          t_last = now
+        if step % args.checkpoint_steps == 0:
+          save_checkpoint(args.train_dir, trainer.state())
+          saved = step
+      if saved != trainer.global_step:
+        save_checkpoint(args.train_dir, trainer.state())
+      write_summary(summ, trainer, batches, time.time() - t_begin)
+    logging.info('Done at step %d', trainer.global_step)
+    return trainer.global_step
+  finally:
+    trainer.close()
+
+
+if __name__ == '__main__':
+  main()
