@@ -159,6 +159,23 @@ class PairDesc(ctypes.Structure):
               ('shape_zyx', ctypes.c_int32 * 3), ('reserved', ctypes.c_int32)]
 
 
+class EvaluationSectionPlan(ctypes.Structure):
+  """ffn_evaluation_section_plan (include/ffn_evaluation.h)."""
+  _fields_ = [('margin_yx', ctypes.c_int32 * 2), ('kind', ctypes.c_int32),
+              ('z0', ctypes.c_int32), ('dy', ctypes.c_int32),
+              ('dx', ctypes.c_int32), ('blank_value', ctypes.c_float),
+              ('blur_sigma', ctypes.c_float)]
+
+
+class EvaluationSection(ctypes.Structure):
+  """ffn_evaluation_section (include/ffn_evaluation.h)."""
+  _fields_ = [('blank_mask', ctypes.c_uint8), ('blur_mask', ctypes.c_uint8),
+              ('gray', ctypes.c_uint8), ('reserved', ctypes.c_uint8),
+              ('blank_yx', ctypes.c_int32 * 2), ('blur_yx', ctypes.c_int32 * 2),
+              ('contrast', ctypes.c_float), ('brightness', ctypes.c_float),
+              ('gamma', ctypes.c_float)]
+
+
 class EvaluationGeometry(ctypes.Structure):
   """ffn_evaluation_geometry (include/ffn_evaluation.h)."""
   _fields_ = [('input_seed_zyx', ctypes.c_int32 * 3),
@@ -393,6 +410,12 @@ SIGNATURES = {
     'ffn_evaluation_last_timing_train': (_I, [_P,
                                               ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double)]),
+    'ffn_evaluation_load_sections': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, ctypes.c_float,
+                                          ctypes.c_float]),
+    'ffn_evaluation_last_timing_sections': (
+        _I, [_P, ctypes.POINTER(ctypes.c_double),
+             ctypes.POINTER(ctypes.c_double)]),
     # include/ffn_gradients.h
     'ffn_gradients_create': (_I, [_I, ctypes.POINTER(_P)]),
     'ffn_gradients_destroy': (None, [_P]),

@@ -14,7 +14,9 @@
 // so the f32 sum does not depend on timing.  load_augmented keeps load's rows
 // while x stays x; where x changes places with y or z it moves 64 x 64 tiles
 // through LDS (row stride 65) so that lanes run along the volume's x on the
-// read and along the slot's x on the write.
+// read and along the slot's x on the write.  load_sections runs one workgroup
+// per (entry, image section) that carries the section's plan out (a blurred
+// section through two LDS planes) into scratch, then that transposing copy.
 //
 // The host validates every box against the geometry before a launch; the
 // kernels take the validated starts.  The per-call descriptors go through a
@@ -24,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -177,10 +180,13 @@ __device__ __forceinline__ int dim_of(const Dims& d, int a) {
   return a == 0 ? d.z : (a == 1 ? d.y : d.x);
 }
 
-template <bool kLabels>
+// kKind 0: the volume's image voxel, normalised; 1: the volume's label as a
+// soft label; 2: the f32 at `it.image`, as it is (load_sections' scratch).
+template <int kKind>
 __device__ __forceinline__ float load_value(const LoadItem& it, long long i,
                                             u64 centre) {
-  if (kLabels) {
+  if (kKind == 2) return static_cast<const float*>(it.image)[i];
+  if (kKind == 1) {
     const u64 l = label_at(it.labels, it.label_elem, i);
     return (l > 0 && l == centre) ? 0.95f : 0.05f;
   }
@@ -192,7 +198,7 @@ __device__ __forceinline__ float load_value(const LoadItem& it, long long i,
 
 // x stays x: load_kernel's row of lanes, the source row picked through the
 // transform and a reflected x read backwards.  q = row of the output patch.
-template <bool kLabels>
+template <int kKind>
 __device__ __forceinline__ void aug_row(const AugItem& a, const int start[3],
                                         Dims S, int q, float* dst, u64 centre,
                                         int lane) {
@@ -205,7 +211,7 @@ __device__ __forceinline__ void aug_row(const AugItem& a, const int start[3],
   float* row = dst + (size_t)q * S.x;
   for (int x = lane; x < S.x; x += 64) {
     const int kx = a.rx ? S.x - 1 - x : x;
-    row[x] = load_value<kLabels>(a.load, src + kx, centre);
+    row[x] = load_value<kKind>(a.load, src + kx, centre);
   }
 }
 
@@ -215,7 +221,7 @@ __device__ __forceinline__ void aug_row(const AugItem& a, const int start[3],
 // volume's x (output a2), values already normalised / turned into soft labels;
 // writing, a wave takes one a2 index per round and its lanes run along the
 // slot's x.  Both sides are contiguous runs of up to kTile voxels.
-template <bool kLabels>
+template <int kKind>
 __device__ __forceinline__ void aug_tile(const AugItem& a, const int start[3],
                                          Dims S, int t, float* dst, u64 centre,
                                          float (*tile)[kTileStride], int wave,
@@ -238,7 +244,7 @@ __device__ __forceinline__ void aug_tile(const AugItem& a, const int start[3],
     const int i2 = tx + r;
     if (i2 < S.x && ia_r < Sa) {
       const int j2 = a.rx ? S.x - 1 - i2 : i2;
-      tile[r][lane] = load_value<kLabels>(a.load, base + j2 * st_p2 + k2, centre);
+      tile[r][lane] = load_value<kKind>(a.load, base + j2 * st_p2 + k2, centre);
     }
   }
   __syncthreads();
@@ -254,21 +260,30 @@ __device__ __forceinline__ void aug_tile(const AugItem& a, const int start[3],
   __syncthreads();
 }
 
-// grid.y = entry.  The branch on x_moves is uniform per workgroup.
+// grid.y = entry.  The branch on x_moves is uniform per workgroup.  kCopy
+// (load_sections): an entry has two items, the first addressing a dense f32
+// image patch and the second a dense f32 label patch (both through
+// load.image, starts 0, their own strides), which are copied as they are.
+template <bool kCopy>
 __global__ __launch_bounds__(kThreads) void load_augmented_kernel(
     const AugItem* __restrict__ items, SlotArrays s, float pad_logit,
     float centre_logit) {
   __shared__ float tile[kTile][kTileStride];
-  const AugItem a = items[blockIdx.y];
+  constexpr int kImage = kCopy ? 2 : 0, kLabel = kCopy ? 2 : 1;
+  const AugItem a = items[kCopy ? 2 * blockIdx.y : blockIdx.y];
+  const AugItem b_item = items[kCopy ? 2 * blockIdx.y + 1 : blockIdx.y];
+  const AugItem& al = kCopy ? b_item : a;  // what addresses the labels
   const LoadItem& it = a.load;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const Dims ip = s.image_patch, lp = s.label_patch;
   const int rc = s.canvas.z * s.canvas.y;
-  const u64 centre = label_at(
-      it.labels, it.label_elem,
-      (it.lab0[0] + lp.z / 2) * it.sy + (it.lab0[1] + lp.y / 2) * it.sx +
-          (it.lab0[2] + lp.x / 2));
+  const u64 centre =
+      kCopy ? 0
+            : label_at(it.labels, it.label_elem,
+                       (it.lab0[0] + lp.z / 2) * it.sy +
+                           (it.lab0[1] + lp.y / 2) * it.sx +
+                           (it.lab0[2] + lp.x / 2));
   float* image = s.image_of(it.slot);
   float* labels = s.labels_of(it.slot);
   float* seed = s.seed_of(it.slot);
@@ -278,9 +293,9 @@ __global__ __launch_bounds__(kThreads) void load_augmented_kernel(
     for (int r = blockIdx.x * kWaves + wave; r < rows;
          r += gridDim.x * kWaves) {
       if (r < ri) {
-        aug_row<false>(a, it.img0, ip, r, image, centre, lane);
+        aug_row<kImage>(a, it.img0, ip, r, image, centre, lane);
       } else if (r < ri + rl) {
-        aug_row<true>(a, it.lab0, lp, r - ri, labels, centre, lane);
+        aug_row<kLabel>(al, al.load.lab0, lp, r - ri, labels, centre, lane);
       } else {
         const int q = r - ri - rl;
         const int z = q / s.canvas.y, y = q - z * s.canvas.y;
@@ -301,9 +316,10 @@ __global__ __launch_bounds__(kThreads) void load_augmented_kernel(
   // (u depends on the workgroup only: every thread meets the same barriers)
   for (int u = blockIdx.x; u < units; u += gridDim.x) {
     if (u < ti) {
-      aug_tile<false>(a, it.img0, ip, u, image, centre, tile, wave, lane);
+      aug_tile<kImage>(a, it.img0, ip, u, image, centre, tile, wave, lane);
     } else if (u < ti + tl) {
-      aug_tile<true>(a, it.lab0, lp, u - ti, labels, centre, tile, wave, lane);
+      aug_tile<kLabel>(al, al.load.lab0, lp, u - ti, labels, centre, tile, wave,
+                        lane);
     } else {
       const int q = (u - ti - tl) * kWaves + wave;
       if (q < rc) {
@@ -315,6 +331,170 @@ __global__ __launch_bounds__(kThreads) void load_augmented_kernel(
       }
     }
   }
+}
+
+// ---- load_sections: the section augmentations, before the transform ----------
+
+constexpr int kMaxRadius = FFN_EVALUATION_MAX_BLUR_RADIUS;
+constexpr int kWeights = kMaxRadius + 1;  // w_0 .. w_r per entry, f64
+constexpr int kLabelBlocks = 64;          // grid.x share of the label rows
+
+// One entry of a load_sections: the load (img0 / lab0 are the starts of the
+// final, unenlarged patches), and the entry's plan as the kernel needs it.
+struct SecItem {
+  LoadItem load;
+  int margin[2];  // y, x
+  int kind, z0, dy, dx;
+  int m[3];       // per-axis maximum of the two loaded sizes
+  int radius;     // of the blur; 0: none
+  float blank_value;
+};
+
+__device__ __forceinline__ int wrap(int p, int n) {
+  p %= n;
+  return p < 0 ? p + n : p;
+}
+
+// Final index i of an axis of final size `fin`, loaded size `loaded`, padded
+// size m -> index into the loaded box (ffn_evaluation.h, misalignment).
+__device__ __forceinline__ int misaligned(int i, int fin, int loaded, int m,
+                                          int shift, bool moved) {
+  int p = i + (m - fin) / 2;
+  if (moved) p = wrap(p + shift, m);
+  const int j = p - (m - loaded) / 2;
+  return j < 0 ? 0 : (j > loaded - 1 ? loaded - 1 : j);
+}
+
+__device__ __forceinline__ bool section_moved(const SecItem& it, int z, int Z) {
+  const int zp = z + (it.m[0] - Z) / 2;
+  return it.kind == 1 ? zp == it.z0 : (it.kind == 2 && zp >= it.z0);
+}
+
+// _quadrant_replace's four regions around the split point.
+__device__ __forceinline__ bool selected(unsigned mask, const int32_t yx[2],
+                                         int y, int x) {
+  const int q = (y >= yx[0] ? 1 : 0) + (x >= yx[1] ? 2 : 0);
+  return (mask >> q) & 1;
+}
+
+// d c b a | a b c d | d c b a: period 2 n.
+__device__ __forceinline__ int reflected(int i, int n) {
+  i = wrap(i, 2 * n);
+  return i < n ? i : 2 * n - 1 - i;
+}
+
+// Grayscale perturbation where asked, then load's normalisation.
+__device__ __forceinline__ float section_finish(
+    float v, const ffn_evaluation_section& sec, const LoadItem& it) {
+  if (sec.gray) {
+    const float nv = __fdiv_rn(v, 255.f);
+    const float a = __fadd_rn(__fmul_rn(nv, sec.contrast), sec.brightness);
+    const float c = fminf(fmaxf(a, 0.f), 1.f);
+    v = __fmul_rn(powf(c, sec.gamma), 255.f);
+  }
+  return (v - it.offset) / it.scale;
+}
+
+// One pass of the blur at (y, x) of plane p (H x W), along y (kAlongX = false)
+// or x: scipy's symmetric correlate1d, in its order, no contraction.
+template <bool kAlongX>
+__device__ __forceinline__ float blur_at(const float* p, int H, int W, int y,
+                                         int x, int r,
+                                         const double* __restrict__ w) {
+  double acc = __dmul_rn((double)p[y * W + x], w[0]);
+  for (int k = r; k >= 1; --k) {
+    const float lo = kAlongX ? p[y * W + reflected(x - k, W)]
+                             : p[reflected(y - k, H) * W + x];
+    const float hi = kAlongX ? p[y * W + reflected(x + k, W)]
+                             : p[reflected(y + k, H) * W + x];
+    acc = __dadd_rn(acc, __dmul_rn(__dadd_rn((double)lo, (double)hi), w[k]));
+  }
+  return (float)acc;
+}
+
+// grid.y = entry.  Workgroups [0, ip.z) of grid.x take one image section
+// each; the others share the label rows, a wave per row as load_kernel.  A
+// section without a blur streams: a wave per row, lanes along x.  A blurred
+// one stages the misaligned, blanked plane in LDS (plane 0), blurs along y
+// into plane 1, then along x; in every pass the lanes of a wave run along x,
+// so consecutive lanes touch consecutive banks whatever the row length, and
+// the only conflicts are the few lanes folded back at a reflected edge.
+// Writes the untransformed, normalised image patch and the soft label patch
+// of entry e densely at image_out[e] / labels_out[e].
+__global__ __launch_bounds__(kThreads) void sections_kernel(
+    const SecItem* __restrict__ items,
+    const ffn_evaluation_section* __restrict__ sections,
+    const double* __restrict__ weights, Dims ip, Dims lp,
+    float* __restrict__ image_out, float* __restrict__ labels_out) {
+  extern __shared__ __attribute__((aligned(16))) float planes[];
+  const SecItem it = items[blockIdx.y];
+  const LoadItem& ld = it.load;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int my = it.margin[0], mx = it.margin[1];
+  if ((int)blockIdx.x >= ip.z) {
+    const u64 centre = label_at(
+        ld.labels, ld.label_elem,
+        (ld.lab0[0] + lp.z / 2) * ld.sy + (ld.lab0[1] + lp.y / 2) * ld.sx +
+            (ld.lab0[2] + lp.x / 2));
+    float* out = labels_out + blockIdx.y * lp.voxels();
+    const int rows = lp.z * lp.y;
+    const int nb = gridDim.x - ip.z;
+    for (int q = ((int)blockIdx.x - ip.z) * kWaves + wave; q < rows;
+         q += nb * kWaves) {
+      const int z = q / lp.y, y = q - z * lp.y;
+      const bool moved = section_moved(it, z, lp.z);
+      const int jy = misaligned(y, lp.y, lp.y + 2 * my, it.m[1], -it.dy, moved);
+      const long long row = (ld.lab0[0] + z) * ld.sy +
+                            (ld.lab0[1] - my + jy) * ld.sx + ld.lab0[2] - mx;
+      for (int x = lane; x < lp.x; x += 64) {
+        const int jx =
+            misaligned(x, lp.x, lp.x + 2 * mx, it.m[2], it.dx, moved);
+        const u64 l = label_at(ld.labels, ld.label_elem, row + jx);
+        out[(size_t)q * lp.x + x] = (l > 0 && l == centre) ? 0.95f : 0.05f;
+      }
+    }
+    return;
+  }
+  const int z = blockIdx.x;
+  const int H = ip.y, W = ip.x;
+  const ffn_evaluation_section sec = sections[blockIdx.y * ip.z + z];
+  const bool moved = section_moved(it, z, ip.z);
+  // (the same in every thread of the workgroup: the barriers below are safe)
+  const int r = sec.blur_mask ? it.radius : 0;
+  float* out = image_out + blockIdx.y * ip.voxels() + (size_t)z * H * W;
+  float* p0 = planes;
+  float* p1 = planes + H * W;
+  for (int y = wave; y < H; y += kWaves) {
+    const int jy = misaligned(y, H, H + 2 * my, it.m[1], -it.dy, moved);
+    const long long row = (ld.img0[0] + z) * ld.sy +
+                          (ld.img0[1] - my + jy) * ld.sx + ld.img0[2] - mx;
+    for (int x = lane; x < W; x += 64) {
+      const int jx = misaligned(x, W, W + 2 * mx, it.m[2], it.dx, moved);
+      float v = ld.image_elem == 1
+                    ? (float)static_cast<const u8*>(ld.image)[row + jx]
+                    : static_cast<const float*>(ld.image)[row + jx];
+      if (selected(sec.blank_mask, sec.blank_yx, y, x)) v = it.blank_value;
+      if (r)
+        p0[y * W + x] = v;
+      else
+        out[y * W + x] = section_finish(v, sec, ld);
+    }
+  }
+  if (!r) return;
+  const double* w = weights + blockIdx.y * kWeights;
+  __syncthreads();
+  for (int y = wave; y < H; y += kWaves)
+    for (int x = lane; x < W; x += 64)
+      p1[y * W + x] = blur_at<false>(p0, H, W, y, x, r, w);
+  __syncthreads();
+  for (int y = wave; y < H; y += kWaves)
+    for (int x = lane; x < W; x += 64) {
+      const float v = selected(sec.blur_mask, sec.blur_yx, y, x)
+                          ? blur_at<true>(p1, H, W, y, x, r, w)
+                          : p0[y * W + x];
+      out[y * W + x] = section_finish(v, sec, ld);
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void probe_kernel(
@@ -586,6 +766,16 @@ struct ffn_evaluation : ffn_unit::Unit {
   PinnedBuf stage;
   double ms[6] = {0, 0, 0, 0, 0, 0}, bytes[6] = {0, 0, 0, 0, 0, 0};
   double ms_train[2] = {0, 0}, bytes_train[2] = {0, 0};
+  // load_sections: the untransformed patches between its two launches, the
+  // event between them, whether sections_kernel may take all of the LDS
+  DevBuf sec_image, sec_labels;
+  hipEvent_t ev_mid = nullptr;
+  bool sec_lds_cleared = false;
+  double ms_sections[2] = {0, 0}, bytes_sections[2] = {0, 0};
+
+  ~ffn_evaluation() {
+    if (ev_mid) (void)hipEventDestroy(ev_mid);
+  }
 
   SlotArrays arrays() const {
     SlotArrays s;
@@ -846,6 +1036,65 @@ double load_bytes(const SlotArrays& s, int n, double volume_bytes) {
                                            s.canvas.voxels());
 }
 
+// The checks of load_augmented's perms / reflects and the transform fields of
+// items[k * stride] for k < n; *blocks = grid.x of load_augmented_kernel.
+int transform_items(const ffn_evaluation* h, int n, const int32_t* perms,
+                    const uint8_t* reflects, AugItem* items, int stride,
+                    int* blocks_out) {
+  if (!perms || !reflects) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  const ffn_evaluation_geometry& g = h->g;
+  const SlotArrays s = h->arrays();
+  const int rc = s.canvas.z * s.canvas.y;
+  auto tiles = [](int n) { return (n + kTile - 1) / kTile; };
+  int blocks = 1;
+  for (int k = 0; k < n; ++k) {
+    const int32_t* perm = perms + 3 * k;
+    const uint8_t* ref = reflects + 3 * k;
+    unsigned seen = 0;
+    for (int a = 0; a < 3; ++a) {
+      if (perm[a] < 0 || perm[a] > 2 || ((seen >> perm[a]) & 1))
+        return ffn_set_error(FFN_ERR_ARG,
+                             "(%d, %d, %d) is not a permutation of 0, 1, 2",
+                             perm[0], perm[1], perm[2]);
+      seen |= 1u << perm[a];
+      if (ref[a] > 1)
+        return ffn_set_error(FFN_ERR_ARG, "reflect value %d is not 0 or 1",
+                             (int)ref[a]);
+    }
+    for (int a = 0; a < 3; ++a)
+      if (perm[a] != a &&
+          (g.image_patch_zyx[a] != g.image_patch_zyx[perm[a]] ||
+           g.label_patch_zyx[a] != g.label_patch_zyx[perm[a]]))
+        return ffn_set_error(FFN_ERR_ARG,
+                             "axes %d and %d change places but differ in patch "
+                             "size", a, perm[a]);
+    AugItem& it = items[k * stride];
+    it.x_moves = perm[2] != 2;
+    it.a2 = it.p2 = it.swap = 0;
+    int units;
+    if (!it.x_moves) {
+      it.swap = perm[0] == 1;
+      it.ra = ref[0];
+      it.rb = ref[1];
+      units = (s.image_patch.z * s.image_patch.y +
+               s.label_patch.z * s.label_patch.y + rc + kWaves - 1) / kWaves;
+    } else {
+      it.a2 = perm[0] == 2 ? 0 : 1;
+      it.p2 = perm[2];
+      const int b = 1 - it.a2;
+      it.ra = ref[it.a2];
+      it.rb = ref[b];
+      units = (rc + kWaves - 1) / kWaves;
+      for (const int32_t* S : {g.image_patch_zyx, g.label_patch_zyx})
+        units += S[b] * tiles(S[it.a2]) * tiles(S[2]);
+    }
+    it.rx = ref[2];
+    if (units > blocks) blocks = units;
+  }
+  *blocks_out = blocks > kRowBlocks ? kRowBlocks : blocks;
+  return FFN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -887,67 +1136,218 @@ int ffn_evaluation_load_augmented(ffn_evaluation* h, int n,
   U_OK(load_items(h, n, slots, volumes, centres_xyz, offsets, scales,
                   [&](int k) -> LoadItem& { return items[k].load; },
                   &volume_bytes));
-  if (!perms || !reflects) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
-  const ffn_evaluation_geometry& g = h->g;
-  const SlotArrays s = h->arrays();
-  const int rc = s.canvas.z * s.canvas.y;
-  auto tiles = [](int n) { return (n + kTile - 1) / kTile; };
   int blocks = 1;
-  for (int k = 0; k < n; ++k) {
-    const int32_t* perm = perms + 3 * k;
-    const uint8_t* ref = reflects + 3 * k;
-    unsigned seen = 0;
-    for (int a = 0; a < 3; ++a) {
-      if (perm[a] < 0 || perm[a] > 2 || ((seen >> perm[a]) & 1))
-        return ffn_set_error(FFN_ERR_ARG,
-                             "(%d, %d, %d) is not a permutation of 0, 1, 2",
-                             perm[0], perm[1], perm[2]);
-      seen |= 1u << perm[a];
-      if (ref[a] > 1)
-        return ffn_set_error(FFN_ERR_ARG, "reflect value %d is not 0 or 1",
-                             (int)ref[a]);
-    }
-    for (int a = 0; a < 3; ++a)
-      if (perm[a] != a &&
-          (g.image_patch_zyx[a] != g.image_patch_zyx[perm[a]] ||
-           g.label_patch_zyx[a] != g.label_patch_zyx[perm[a]]))
-        return ffn_set_error(FFN_ERR_ARG,
-                             "axes %d and %d change places but differ in patch "
-                             "size", a, perm[a]);
-    AugItem& it = items[k];
-    it.x_moves = perm[2] != 2;
-    it.a2 = it.p2 = it.swap = 0;
-    int units;
-    if (!it.x_moves) {
-      it.swap = perm[0] == 1;
-      it.ra = ref[0];
-      it.rb = ref[1];
-      units = (s.image_patch.z * s.image_patch.y +
-               s.label_patch.z * s.label_patch.y + rc + kWaves - 1) / kWaves;
-    } else {
-      it.a2 = perm[0] == 2 ? 0 : 1;
-      it.p2 = perm[2];
-      const int b = 1 - it.a2;
-      it.ra = ref[it.a2];
-      it.rb = ref[b];
-      units = (rc + kWaves - 1) / kWaves;
-      for (const int32_t* S : {g.image_patch_zyx, g.label_patch_zyx})
-        units += S[b] * tiles(S[it.a2]) * tiles(S[2]);
-    }
-    it.rx = ref[2];
-    if (units > blocks) blocks = units;
-  }
-  if (blocks > kRowBlocks) blocks = kRowBlocks;
+  U_OK(transform_items(h, n, perms, reflects, items, 1, &blocks));
+  const SlotArrays s = h->arrays();
   U_OK(send_items(h, items, n * sizeof(AugItem)));
   double ms = 0.0;
   U_OK(h->timer_start());
-  hipLaunchKernelGGL(load_augmented_kernel, dim3(blocks, n), dim3(kThreads), 0,
+  hipLaunchKernelGGL(load_augmented_kernel<false>, dim3(blocks, n),
+                     dim3(kThreads), 0,
                      h->stream, static_cast<const AugItem*>(h->items.p), s,
                      seed_pad_logit, seed_centre_logit);
   U_TRY(hipGetLastError());
   U_OK(h->timer_stop(&ms));
   h->ms_train[0] = ms;
   h->bytes_train[0] = load_bytes(s, n, volume_bytes);
+  return FFN_OK;
+}
+
+int ffn_evaluation_load_sections(
+    ffn_evaluation* h, int n, const int32_t* slots, const int32_t* volumes,
+    const int32_t* centres_xyz, const float* offsets, const float* scales,
+    const int32_t* perms, const uint8_t* reflects,
+    const ffn_evaluation_section_plan* plans,
+    const ffn_evaluation_section* sections, float seed_pad_logit,
+    float seed_centre_logit) {
+  SecItem items[kMaxSlots];
+  AugItem copies[2 * kMaxSlots];
+  double volume_bytes = 0.0;
+  U_OK(load_items(h, n, slots, volumes, centres_xyz, offsets, scales,
+                  [&](int k) -> LoadItem& { return items[k].load; },
+                  &volume_bytes));
+  int blocks = 1;
+  U_OK(transform_items(h, n, perms, reflects, copies, 2, &blocks));
+  if (!plans || !sections) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  const ffn_evaluation_geometry& g = h->g;
+  const SlotArrays s = h->arrays();
+  const Dims ip = s.image_patch, lp = s.label_patch;
+  std::vector<double> weights((size_t)n * kWeights, 0.0);
+  bool any_blur = false;
+  for (int k = 0; k < n; ++k) {
+    const ffn_evaluation_section_plan& p = plans[k];
+    SecItem& it = items[k];
+    const Volume& v = *h->volumes[volumes[k]];
+    if (p.margin_yx[0] < 0 || p.margin_yx[1] < 0 || p.margin_yx[0] > 4096 ||
+        p.margin_yx[1] > 4096)
+      return ffn_set_error(FFN_ERR_ARG, "margin (%d, %d) of entry %d",
+                           p.margin_yx[0], p.margin_yx[1], k);
+    if (p.kind < 0 || p.kind > 2)
+      return ffn_set_error(FFN_ERR_ARG, "misalignment kind %d is not 0, 1, 2",
+                           p.kind);
+    it.margin[0] = p.margin_yx[0];
+    it.margin[1] = p.margin_yx[1];
+    it.m[0] = ip.z > lp.z ? ip.z : lp.z;
+    it.m[1] = (ip.y > lp.y ? ip.y : lp.y) + 2 * it.margin[0];
+    it.m[2] = (ip.x > lp.x ? ip.x : lp.x) + 2 * it.margin[1];
+    if (p.z0 < 0 || p.z0 >= it.m[0])
+      return ffn_set_error(FFN_ERR_ARG, "z0 %d outside [0, %d)", p.z0, it.m[0]);
+    if (p.dy < -it.m[1] || p.dy > it.m[1] || p.dx < -it.m[2] ||
+        p.dx > it.m[2])
+      return ffn_set_error(FFN_ERR_ARG,
+                           "misalignment offset (%d, %d) exceeds the padded "
+                           "size (%d, %d)", p.dy, p.dx, it.m[1], it.m[2]);
+    it.kind = p.kind;
+    it.z0 = p.z0;
+    it.dy = p.dy;
+    it.dx = p.dx;
+    it.blank_value = p.blank_value;
+    // (a NaN fails the first comparison)
+    if (!(p.blur_sigma >= 0.f) || !(p.blur_sigma <= 16.f))
+      return ffn_set_error(FFN_ERR_ARG, "blur_sigma %g of entry %d",
+                           (double)p.blur_sigma, k);
+    const double sigma = (double)p.blur_sigma;
+    it.radius = (int)(4.0 * sigma + 0.5);
+    if (it.radius > kMaxRadius)
+      return ffn_set_error(FFN_ERR_ARG, "blur_sigma %g gives radius %d > %d",
+                           sigma, it.radius, kMaxRadius);
+    double* w = weights.data() + (size_t)k * kWeights;
+    w[0] = 1.0;
+    if (it.radius > 0) {
+      // scipy's _gaussian_kernel1d: exp(-0.5 / sigma^2 * x^2) over x = -r .. r,
+      // divided by its sum
+      const double c = -0.5 / (sigma * sigma);
+      double sum = 0.0;
+      for (int x = -it.radius; x <= it.radius; ++x)
+        sum += std::exp(c * (double)(x * x));
+      for (int x = 0; x <= it.radius; ++x)
+        w[x] = std::exp(c * (double)(x * x)) / sum;
+    }
+    bool blurred = false;
+    for (int z = 0; z < ip.z; ++z) {
+      const ffn_evaluation_section& sec = sections[(size_t)k * ip.z + z];
+      if (sec.blank_mask > 15 || sec.blur_mask > 15 || sec.gray > 1)
+        return ffn_set_error(FFN_ERR_ARG,
+                             "section %d of entry %d: masks (%d, %d), gray %d",
+                             z, k, (int)sec.blank_mask, (int)sec.blur_mask,
+                             (int)sec.gray);
+      for (const int32_t* yx : {sec.blank_yx, sec.blur_yx})
+        if (yx[0] < 0 || yx[0] > ip.y || yx[1] < 0 || yx[1] > ip.x)
+          return ffn_set_error(FFN_ERR_ARG,
+                               "split point (%d, %d) outside the %d x %d "
+                               "section", yx[0], yx[1], ip.y, ip.x);
+      if (sec.gray &&
+          (!std::isfinite(sec.contrast) || !std::isfinite(sec.brightness) ||
+           !std::isfinite(sec.gamma) || !(sec.gamma > 0.f)))
+        return ffn_set_error(FFN_ERR_ARG,
+                             "grayscale factors (%g, %g, %g) of section %d",
+                             (double)sec.contrast, (double)sec.brightness,
+                             (double)sec.gamma, z);
+      if (sec.blur_mask && it.radius > 0) blurred = true;
+    }
+    if (blurred && (long long)ip.y * ip.x > FFN_EVALUATION_MAX_BLUR_PLANE)
+      return ffn_set_error(FFN_ERR_ARG,
+                           "a blur on a %d x %d section: at most %d voxels",
+                           ip.y, ip.x, FFN_EVALUATION_MAX_BLUR_PLANE);
+    any_blur = any_blur || blurred;
+    // the enlarged boxes (z has no margin: load_items checked it)
+    for (int a = 1; a < 3; ++a) {
+      const long long mg = it.margin[a - 1];
+      if (it.load.img0[a] - mg < 0 ||
+          it.load.img0[a] + g.image_patch_zyx[a] + mg > v.shape[a] ||
+          it.load.lab0[a] - mg < 0 ||
+          it.load.lab0[a] + g.label_patch_zyx[a] + mg > v.shape[a])
+        return ffn_set_error(FFN_ERR_ARG,
+                             "the patches around (%d, %d, %d) xyz with margin "
+                             "(%d, %d) leave volume %d", centres_xyz[3 * k],
+                             centres_xyz[3 * k + 1], centres_xyz[3 * k + 2],
+                             it.margin[0], it.margin[1], volumes[k]);
+    }
+  }
+  U_OK(ensure(h->sec_image, (size_t)n * ip.voxels() * sizeof(float)));
+  U_OK(ensure(h->sec_labels, (size_t)n * lp.voxels() * sizeof(float)));
+  if (!h->ev_mid) U_TRY(hipEventCreate(&h->ev_mid));
+  const size_t lds = any_blur ? 2 * (size_t)ip.y * ip.x * sizeof(float) : 0;
+  if (lds > 48 * 1024 && !h->sec_lds_cleared) {
+    U_TRY(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&sections_kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        2 * FFN_EVALUATION_MAX_BLUR_PLANE * (int)sizeof(float)));
+    h->sec_lds_cleared = true;
+  }
+  // the second launch copies the scratch patches: dense, starts 0
+  for (int k = 0; k < n; ++k) {
+    for (int which = 0; which < 2; ++which) {
+      AugItem& c = copies[2 * k + which];
+      if (which) c = copies[2 * k];  // the transform
+      const Dims d = which ? lp : ip;
+      LoadItem& l = c.load;
+      l.image = static_cast<float*>(which ? h->sec_labels.p : h->sec_image.p) +
+                (size_t)k * d.voxels();
+      l.labels = nullptr;
+      l.sy = (long long)d.y * d.x;
+      l.sx = d.x;
+      l.image_elem = 4;
+      l.label_elem = 4;
+      l.slot = slots[k];
+      l.offset = 0.f;
+      l.scale = 1.f;
+      for (int a = 0; a < 3; ++a) l.img0[a] = l.lab0[a] = 0;
+    }
+  }
+  // one blob: SecItem[n] | AugItem[2 n] | sections [n][z] | weights [n][32]
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t off_copies = up16(n * sizeof(SecItem));
+  const size_t off_sections = up16(off_copies + 2 * n * sizeof(AugItem));
+  const size_t sections_bytes =
+      (size_t)n * ip.z * sizeof(ffn_evaluation_section);
+  const size_t off_weights = up16(off_sections + sections_bytes);
+  const size_t total = off_weights + weights.size() * sizeof(double);
+  std::vector<char> blob(total, 0);
+  std::memcpy(blob.data(), items, n * sizeof(SecItem));
+  std::memcpy(blob.data() + off_copies, copies, 2 * n * sizeof(AugItem));
+  std::memcpy(blob.data() + off_sections, sections, sections_bytes);
+  std::memcpy(blob.data() + off_weights, weights.data(),
+              weights.size() * sizeof(double));
+  U_OK(send_items(h, blob.data(), total));
+  const char* dev = static_cast<const char*>(h->items.p);
+  int label_blocks = (lp.z * lp.y + kWaves - 1) / kWaves;
+  if (label_blocks > kLabelBlocks) label_blocks = kLabelBlocks;
+  U_OK(h->timer_start());
+  hipLaunchKernelGGL(
+      sections_kernel, dim3(ip.z + label_blocks, n), dim3(kThreads), lds,
+      h->stream, reinterpret_cast<const SecItem*>(dev),
+      reinterpret_cast<const ffn_evaluation_section*>(dev + off_sections),
+      reinterpret_cast<const double*>(dev + off_weights), ip, lp,
+      static_cast<float*>(h->sec_image.p),
+      static_cast<float*>(h->sec_labels.p));
+  U_TRY(hipGetLastError());
+  U_TRY(hipEventRecord(h->ev_mid, h->stream));
+  hipLaunchKernelGGL(load_augmented_kernel<true>, dim3(blocks, n),
+                     dim3(kThreads), 0, h->stream,
+                     reinterpret_cast<const AugItem*>(dev + off_copies), s,
+                     seed_pad_logit, seed_centre_logit);
+  U_TRY(hipGetLastError());
+  double ms = 0.0;
+  U_OK(h->timer_stop(&ms));
+  float first = 0.f;
+  U_TRY(hipEventElapsedTime(&first, h->ev0, h->ev_mid));
+  h->ms_sections[0] = ms;
+  h->ms_sections[1] = first;
+  h->bytes_sections[0] = load_bytes(s, n, volume_bytes);
+  h->bytes_sections[1] =
+      volume_bytes + 4.0 * n * (double)(ip.voxels() + lp.voxels());
+  return FFN_OK;
+}
+
+int ffn_evaluation_last_timing_sections(ffn_evaluation* h, double kernel_ms[2],
+                                        double algorithmic_bytes[2]) {
+  if (!h || !kernel_ms || !algorithmic_bytes)
+    return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  for (int k = 0; k < 2; ++k) {
+    kernel_ms[k] = h->ms_sections[k];
+    algorithmic_bytes[k] = h->bytes_sections[k];
+  }
   return FFN_OK;
 }
 

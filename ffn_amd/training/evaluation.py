@@ -19,7 +19,9 @@ and mesh summaries, weighted or sampled coordinate sources.
 
 For training the unit also has `load_augmented` (load with
 train.py's PermuteAndReflect) and `gather_train` (gather plus the labels of the
-FoV); `FovWalk` holds the host halves of the move policies for this module's
+FoV) and `load_sections` (load_augmented with the section augmentations of
+augmentation.SectionPlan carried out on the device); `FovWalk`
+holds the host halves of the move policies for this module's
 CheckpointEvaluator and for examples.BatchExampleIter.
 """
 
@@ -46,6 +48,10 @@ MAX_SLOTS = 32
 EVAL_PROBABILITY = 0.9
 CALL_KINDS = ('load', 'probe_moves', 'gather', 'paste', 'score_faces', 'finish')
 TRAIN_CALL_KINDS = ('load_augmented', 'gather_train')
+SECTION_CALL_KINDS = ('load_sections', 'sections_kernel')
+#: numpy views of the ctypes mirrors of ffn_evaluation_section_plan / _section
+PLAN_DTYPE = np.dtype(_lib.EvaluationSectionPlan)
+SECTION_DTYPE = np.dtype(_lib.EvaluationSection)
 
 
 def logit(p) -> float:
@@ -135,6 +141,26 @@ class DeviceArray:
 def _i32(values, shape=None) -> np.ndarray:
   out = np.ascontiguousarray(values, dtype=np.int32)
   return out if shape is None else out.reshape(shape)
+
+
+def section_plan_arrays(plans, sections: int):
+  """augmentation.SectionPlans -> (ffn_evaluation_section_plan [n],
+  ffn_evaluation_section [n, sections]) as numpy arrays of the C layout."""
+  c_plans = np.zeros(len(plans), PLAN_DTYPE)
+  c_sections = np.zeros((len(plans), sections), SECTION_DTYPE)
+  for k, p in enumerate(plans):
+    if p.sections != sections:
+      raise ValueError('a plan for %d sections, the image patch has %d' %
+                       (p.sections, sections))
+    c_plans['margin_yx'][k] = p.margin_yx
+    for name in ('kind', 'z0', 'dy', 'dx', 'blank_value', 'blur_sigma'):
+      c_plans[name][k] = getattr(p, name)
+    for name in ('blank_mask', 'blur_mask', 'gray', 'blank_yx', 'blur_yx'):
+      c_sections[name][k] = getattr(p, name)
+    c_sections['contrast'][k] = p.factors[:, 0]
+    c_sections['brightness'][k] = p.factors[:, 1]
+    c_sections['gamma'][k] = p.factors[:, 2]
+  return c_plans, c_sections
 
 
 class EvaluationOps(_unit.Handle):
@@ -242,6 +268,50 @@ class EvaluationOps(_unit.Handle):
           centres.ctypes.data, offsets.ctypes.data, scales.ctypes.data,
           perms.ctypes.data, reflects.ctypes.data,
           float(f32_logit(seed_pad)), float(f32_logit(0.95))))
+
+  def load_sections(self, slots, volumes, centres_xyz, offsets, scales,
+                    perms, reflects, plans, seed_pad: float):
+    """load_augmented() with the section augmentations of `plans` (one
+    augmentation.SectionPlan per slot) carried out on the device between
+    reading the volume and the normalisation: misalignment of image and
+    labels, then missing section, out of focus and grayscale perturbation of
+    the image (include/ffn_evaluation.h).  Plans without an operation write
+    what load_augmented() writes.  Raises, touching no slot, on what
+    load_augmented() refuses, on a plan the header refuses, and where the
+    patches enlarged by a plan's margins leave their volume."""
+    slots = _i32(slots)
+    volumes = _i32(volumes)
+    centres = _i32(centres_xyz, (-1, 3))
+    offsets = np.ascontiguousarray(offsets, dtype=np.float32)
+    scales = np.ascontiguousarray(scales, dtype=np.float32)
+    perms = _i32(perms, (-1, 3))
+    reflects_in = np.asarray(reflects).reshape(-1, 3)
+    if ((reflects_in < 0) | (reflects_in > 255)).any():  # the library sees u8
+      raise ValueError('a reflect value is 0 or 1')
+    reflects = np.ascontiguousarray(reflects_in, dtype=np.uint8)
+    plans = list(plans)
+    if not (len(slots) == len(volumes) == len(centres) == len(offsets) ==
+            len(scales) == len(perms) == len(reflects) == len(plans)):
+      raise ValueError('one volume, centre, offset, scale, perm, reflect and '
+                       'plan per slot')
+    sections = self.geometry.image_patch[0]
+    c_plans, c_sections = section_plan_arrays(plans, sections)
+    with self.lock:
+      check(self._lib.ffn_evaluation_load_sections(
+          self._h, len(slots), slots.ctypes.data, volumes.ctypes.data,
+          centres.ctypes.data, offsets.ctypes.data, scales.ctypes.data,
+          perms.ctypes.data, reflects.ctypes.data,
+          c_plans.ctypes.data, c_sections.ctypes.data,
+          float(f32_logit(seed_pad)), float(f32_logit(0.95))))
+
+  def last_timing_sections(self) -> Dict[str, Tuple[float, float]]:
+    """last_timing() of the last load_sections: the whole call and its first
+    launch, the section kernel."""
+    ms = (ctypes.c_double * 2)()
+    nbytes = (ctypes.c_double * 2)()
+    check(self._lib.ffn_evaluation_last_timing_sections(self._h, ms, nbytes))
+    return {kind: (ms[k], nbytes[k])
+            for k, kind in enumerate(SECTION_CALL_KINDS)}
 
   def probe_moves(self, slots, offsets_xyz, seed_threshold: float,
                   label_threshold: float):

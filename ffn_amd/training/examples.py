@@ -5,10 +5,12 @@ voxel arrays resident on the GPU.
 `BatchExampleIter` keeps `batch_size` slots of an EvaluationOps busy, one
 independent example stream per slot as in the reference's `_batch_gen`.  A
 stream loads the next coordinate with a freshly sampled PermuteAndReflect
-transform (EvaluationOps.load_augmented), walks the FoV offsets of its move
-policy (evaluation.FovWalk, the same walk CheckpointEvaluator runs), and when
-they are exhausted scores the slot with `finish` into an EvalResult, as
-get_example calls EvalTracker.add_patch, before it takes the next coordinate.
+transform (EvaluationOps.load_augmented; with `sections`, also a freshly
+sampled plan of section augmentations, EvaluationOps.load_sections), walks
+the FoV offsets of its move policy (evaluation.FovWalk, the same walk
+CheckpointEvaluator runs), and when they are exhausted scores the slot with
+`finish` into an EvalResult, as get_example calls EvalTracker.add_patch,
+before it takes the next coordinate.
 `next()` hands out the seed, image, label and weight arrays of one FoV per
 slot as device arrays; `update_seeds()` pastes the network's logits back.
 The host sees probe results, face maxima and the finish sums only: no voxel
@@ -35,14 +37,17 @@ TRAIN_POLICIES = ('fixed', 'max_pred_moves')
 IDENTITY = ((0, 1, 2), (0, 0, 0))
 
 
-def fits(centre_xyz, shape_zyx, geometry) -> bool:
-  """Whether the image and label patches around a centre stay inside a volume
-  of `shape_zyx` (the reference would fail in a reshape otherwise)."""
+def fits(centre_xyz, shape_zyx, geometry, margin_yx=(0, 0)) -> bool:
+  """Whether the image and label patches around a centre, enlarged by
+  `margin_yx` voxels on both sides of y and x (what the section augmentations
+  read), stay inside a volume of `shape_zyx` (the reference would fail in a
+  reshape otherwise)."""
+  margins = (0, int(margin_yx[0]), int(margin_yx[1]))
   for axis in range(3):
     c = int(centre_xyz[2 - axis])
     for size in (geometry.image_patch[axis], geometry.label_patch[axis]):
-      start = c - (size - 1) // 2
-      if start < 0 or start + size > shape_zyx[axis]:
+      start = c - (size - 1) // 2 - margins[axis]
+      if start < 0 or start + size + 2 * margins[axis] > shape_zyx[axis]:
         return False
   return True
 
@@ -83,8 +88,15 @@ class BatchExampleIter:
   io: (seed, image, labels, weights) device arrays the caller made (what the
     trainer takes: torch tensors); default: the unit's own buffers and
     `weights` None.
+  sections: an augmentation.SectionAugmentations (anything with `sample(image
+    patch zyx, label patch zyx)` -> SectionPlan and `margin_yx`); a plan is
+    sampled for every example started, after the transform, from the sections'
+    own generator, and the example is loaded with EvaluationOps.load_sections.
+    Coordinates whose patches enlarged by the margin leave their volume are
+    skipped.  None: load_augmented, as before.
   keep_history: keep, per example started, its coordinate index, transform,
-    offsets and records in `history` (tests; it grows without bound).
+    offsets and records (and its section plan under 'plan') in `history`
+    (tests; it grows without bound).
   """
 
   def __init__(self, info, ops, volumes, coordinates, fov_policy: str = 'fixed',
@@ -92,7 +104,7 @@ class BatchExampleIter:
                seed_pad: float = 0.05, shifts: Optional[Sequence] = None,
                shuffle_moves: bool = False, moves_seed: Optional[int] = None,
                transform=None, shuffle_seed: Optional[int] = None, io=None,
-               keep_history: bool = False):
+               keep_history: bool = False, sections=None):
     if fov_policy not in TRAIN_POLICIES:
       raise ValueError('fov_policy is one of %r, got %r' %
                        (TRAIN_POLICIES, fov_policy))
@@ -111,6 +123,12 @@ class BatchExampleIter:
           raise ValueError('axes %d and %d may change places but differ in '
                            'patch size' % (p, q))
     self.transform = transform
+    self.sections = sections
+    margin_yx = (0, 0) if sections is None else tuple(sections.margin_yx)
+    #: per-augmentation counts of the reference's summaries, since the start
+    self.section_counts = {'examples': 0, 'misalignment': 0,
+                           'missing_sections': 0, 'outoffocus_sections': 0,
+                           'grayscale': 0}
     self.seed_pad = float(seed_pad)
     self.threshold = evaluation.logit(threshold)
     self.label_threshold = evaluation.expit(self.threshold)
@@ -139,7 +157,7 @@ class BatchExampleIter:
     for centre, name in coordinates:
       if name not in self._volumes:
         raise KeyError('no volume named %r' % (name,))
-      if fits(centre, self._volumes[name][1], g):
+      if fits(centre, self._volumes[name][1], g, margin_yx):
         self.coordinates.append((tuple(int(v) for v in centre), name))
       else:
         self.skipped += 1
@@ -174,6 +192,15 @@ class BatchExampleIter:
   def reset_result(self):
     """EvalTracker.reset: a fresh `result` for the next summary interval."""
     self.result = evaluation.EvalResult(self.shifts)
+
+  def _count_sections(self, plan):
+    summary = plan.summary()
+    counts = self.section_counts
+    counts['examples'] += 1
+    counts['misalignment'] += summary['misalignment_z'] >= 0
+    counts['missing_sections'] += len(summary['missing_z'])
+    counts['outoffocus_sections'] += len(summary['outoffocus_z'])
+    counts['grayscale'] += summary['grayscale']
 
   def _next_coordinate(self) -> int:
     if not self._order:
@@ -213,7 +240,7 @@ class BatchExampleIter:
                            'below the move threshold')
       fresh = [s for s in need if streams[s].example is None]
       if fresh:
-        rows, perms, reflects = [], [], []
+        rows, perms, reflects, plans = [], [], [], []
         for s in fresh:
           index = self._next_coordinate()
           perm, reflect = (self.transform.sample() if self.transform is not None
@@ -226,14 +253,25 @@ class BatchExampleIter:
                    'perm': tuple(int(v) for v in perm),
                    'reflect': tuple(int(v) for v in reflect),
                    'offsets': [], 'records': []}
+          if self.sections is not None:
+            plan = self.sections.sample(self.geometry.image_patch,
+                                        self.geometry.label_patch)
+            plans.append(plan)
+            entry['plan'] = plan
+            self._count_sections(plan)
           self._current[s] = entry
           if self.keep_history:
             self.history.append(entry)
           self.examples_started += 1
         vols = [self._volumes[name] for _, name in rows]
-        ops.load_augmented(fresh, [v[0] for v in vols], [c for c, _ in rows],
-                           [v[2] for v in vols], [v[3] for v in vols], perms,
-                           reflects, self.seed_pad)
+        if self.sections is None:
+          ops.load_augmented(fresh, [v[0] for v in vols], [c for c, _ in rows],
+                             [v[2] for v in vols], [v[3] for v in vols], perms,
+                             reflects, self.seed_pad)
+        else:
+          ops.load_sections(fresh, [v[0] for v in vols], [c for c, _ in rows],
+                            [v[2] for v in vols], [v[3] for v in vols], perms,
+                            reflects, plans, self.seed_pad)
       pairs = [(s, o) for s in need for o in self.walk.candidates(streams[s])]
       probed = {s: {} for s in need}
       if pairs:

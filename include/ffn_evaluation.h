@@ -208,6 +208,106 @@ int ffn_evaluation_io_labels(ffn_evaluation* h, float** labels_dev);
 int ffn_evaluation_last_timing_train(ffn_evaluation* h, double kernel_ms[2],
                                      double algorithmic_bytes[2]);
 
+/* ---- section augmentations (ffn/training/augmentation.py: misalignment,
+ * missing_section, out_of_focus_section, grayscale_perturb) --------------------
+ *
+ * load_sections is load_augmented with a plan per entry that is carried out
+ * between reading the volume and load's normalisation.  The plan holds
+ * decisions only (the caller samples them); the voxel work is the device's.
+ * All image arithmetic is f32 on the voxel converted to f32, i.e. what the
+ * reference's functions compute when they are handed the patch cast to
+ * float32.  (Handed a uint8 patch they truncate after every operation; that
+ * is NOT reproduced.)  In this order:
+ *
+ * 1. Misalignment, on the image and the labels.  An array whose slot size
+ *    ("final" size) is (Z, Hf, Wf) is taken from the volume as the box of
+ *    size (Z, H, W) = (Z, Hf + 2 margin_y, Wf + 2 margin_x) around the same
+ *    centre voxel.  M is the per-axis maximum of the two boxes (image,
+ *    labels), z included.  Section z of an array is moved when, with zp = z +
+ *    (M_z - Z) / 2, zp == z0 (kind 1, slip) or zp >= z0 (kind 2,
+ *    translation).  Final index y reads the box at row
+ *      clamp(p - (M_y - H) / 2, 0, H - 1),  p = y + (M_y - Hf) / 2,
+ *    with p replaced by (p - dy) mod M_y in a moved section; x likewise with
+ *    (p + dx) mod M_x.  Divisions are integer; mod is non-negative.  This is
+ *    np.roll(., dy, y) and np.roll(., -dx, x) on the arrays edge-padded to M,
+ *    then the centre crop, as the reference's misalignment() does it.  No
+ *    read leaves the box.  labels[p] is load's soft 0.95 / 0.05 of the label
+ *    at the mapped index against the label at the centre index of the final,
+ *    unmoved label patch.
+ * 2. Missing section, image only, final image-patch coordinates: a voxel (y,
+ *    x) of section z selected by blank_mask becomes blank_value.  Mask bit 0
+ *    selects [0:sy, 0:sx], bit 1 [sy:, 0:sx], bit 2 [0:sy, sx:], bit 3 [sy:,
+ *    sx:] with (sy, sx) the split point (_quadrant_replace); a whole section
+ *    is bit 3 with the split point (0, 0).
+ * 3. Out of focus: a voxel selected by blur_mask takes the value of the
+ *    Gaussian blur of its section as it is after step 2.  The blur is
+ *    scipy.ndimage.gaussian_filter's: radius r = (int)(4 sigma + 0.5) from
+ *    blur_sigma widened to double, weights w_k = exp(-k^2 / (2 sigma^2)) / sum
+ *    in double (computed by the library on the host), along y, the result
+ *    rounded to f32, then along x, rounded to f32; boundary `reflect` (d c b
+ *    a | a b c d | d c b a, period 2 n, so r may exceed the plane).  One
+ *    output is w_0 v_0 + sum for k = r .. 1 of (v_-k + v_+k) w_k, every
+ *    operation a double one, in this order, none contracted.  r == 0 is the
+ *    identity.
+ * 4. Grayscale, where gray = 1: n = v / 255; a = n * contrast; a = a +
+ *    brightness; c = min(max(a, 0), 1); v = powf(c, gamma) * 255.  Every
+ *    operation up to c is one IEEE f32 operation (no fused multiply-add), so c
+ *    is what numpy computes; powf is the device's; the last product is an
+ *    IEEE f32 one.
+ * Then load's (v - offset) / scale, then load_augmented's transform of the
+ * image and label patches.  The seed canvas is load's.
+ *
+ * A plan of zeros writes what load_augmented writes, bit for bit.
+ *
+ * FFN_ERR_ARG, no slot touched: whatever load_augmented refuses; a negative
+ * margin, or one above 4096 (the largest size configure takes); kind not 0,
+ * 1, 2; z0 outside [0, M_z); |dy| > M_y or |dx| > M_x; a mask above 15 or a
+ * gray above 1; a split point outside [0, Hf] x [0, Wf]; a blur_sigma that is
+ * negative or NaN or gives r > 31 (any sigma above 16, an infinite one
+ * included, is refused before r is formed); with gray = 1 a gamma <= 0 or a
+ * contrast, brightness or gamma that is not finite; an enlarged box
+ * that leaves its volume; a blur (a non-zero blur_mask with r > 0) on an
+ * image plane of more than 128 x 128 = 16384 voxels (the section and its
+ * intermediate stay in the 160 KiB of LDS; larger planes are refused, not
+ * tiled).
+ *
+ * Two launches: the augmented, untransformed patches go to scratch owned by
+ * the handle, then load_augmented's transposing copy fills the slots. */
+#define FFN_EVALUATION_MAX_BLUR_RADIUS 31
+#define FFN_EVALUATION_MAX_BLUR_PLANE 16384
+
+typedef struct ffn_evaluation_section_plan { /* one per entry */
+  int32_t margin_yx[2];
+  int32_t kind; /* 0 none, 1 slip, 2 translation */
+  int32_t z0, dy, dx;
+  float blank_value;
+  float blur_sigma;
+} ffn_evaluation_section_plan;
+
+typedef struct ffn_evaluation_section { /* one per entry and image section */
+  uint8_t blank_mask, blur_mask; /* 4 quadrant bits each */
+  uint8_t gray;                  /* 0 / 1 */
+  uint8_t reserved;              /* 0 */
+  int32_t blank_yx[2], blur_yx[2]; /* split points */
+  float contrast, brightness, gamma;
+} ffn_evaluation_section;
+
+/* plans: n entries; sections: dense [n][image_patch_zyx[0]]. */
+int ffn_evaluation_load_sections(
+    ffn_evaluation* h, int n, const int32_t* slots, const int32_t* volumes,
+    const int32_t* centres_xyz, const float* offsets, const float* scales,
+    const int32_t* perms, const uint8_t* reflects,
+    const ffn_evaluation_section_plan* plans,
+    const ffn_evaluation_section* sections, float seed_pad_logit,
+    float seed_centre_logit);
+
+/* As last_timing_train, of the last load_sections: index 0 the whole call
+ * (both launches; bytes as load), index 1 its first launch alone, the section
+ * kernel (the volume voxels of the two final patches read, their two f32
+ * arrays written). */
+int ffn_evaluation_last_timing_sections(ffn_evaluation* h, double kernel_ms[2],
+                                        double algorithmic_bytes[2]);
+
 #ifdef __cplusplus
 }
 #endif

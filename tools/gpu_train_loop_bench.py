@@ -4,7 +4,7 @@ trainer.train_step_device) and what its two new kernels cost.  Reports;
 asserts nothing.
 
   python tools/gpu_train_loop_bench.py [--size 250] [--steps 40]
-      [--batches 1,8,16] [--kernel-batches 1,32] [--repeats 20]
+      [--batches 1,8,16] [--kernel-batches 1,32] [--repeats 20] [--sections]
 
 Part 1: one synthetic size^3 volume (ffn_amd/synthetic.py cells phantom and its
 labels), the FIB-25 geometry and weights (33^3 FoV, depth 12, deltas 8), policy
@@ -17,6 +17,13 @@ Part 2: HIP-event kernel times (ffn_evaluation_last_timing /
 last_timing_train; median of `repeats` calls after two warm-up calls) on 49^3
 patches at batch 1 and 32: load_augmented with the identity, an x reflection,
 an x-y swap and a z-x swap against load, and gather_train against gather.
+
+--sections: part 1 runs every batch size a second time with the section
+augmentations on (SECTIONS below: all four, never skipped), and part 2 adds
+load_sections (ffn_evaluation_last_timing_sections: the whole call, and its
+first launch alone) with an empty plan and with a full one: a translation by
+(4, -4) from the middle section, two blanked sections, a blur of sigma 2
+(radius 8) on every fourth section, grayscale factors on all of them.
 """
 import argparse
 import collections
@@ -38,7 +45,14 @@ from ffn_amd.training import optimizer  # noqa: E402
 from ffn_amd.training import trainer as trainer_lib  # noqa: E402
 from ffn_amd.training.models import convstack_3d  # noqa: E402
 
-COUNTED = ('load_augmented', 'probe_moves', 'gather_train', 'paste', 'finish')
+COUNTED = ('load_augmented', 'load_sections', 'probe_moves', 'gather_train',
+           'paste', 'finish')
+SECTIONS = dict(misalignment_skip_ratio=0.0, max_xy_offset=4,
+                slip_vs_translate_ratio=0.5, missing_section_skip_ratio=0.0,
+                max_missing_section_indices_ratio=0.05,
+                outoffocus_skip_ratio=0.0, max_outoffocus_indices_ratio=0.25,
+                max_filter_stdev=2.0, grayscale_skip_ratio=0.0,
+                max_contrast_factor=0.3, max_brightness_factor=0.3)
 TRANSFORMS = [('identity', (0, 1, 2), (0, 0, 0)),
               ('x-reflect', (0, 1, 2), (0, 0, 1)),
               ('xy-swap', (0, 2, 1), (0, 0, 0)),
@@ -83,9 +97,12 @@ def coordinates_of(labels, n, margin, seed):
   return [((int(x), int(y), int(z)), 'vol') for z, y, x in picks]
 
 
-def loop_part(model, volumes, coords, batches, steps):
+def loop_part(model, volumes, coords, batches, steps, with_sections=False):
   ops = CountedOps(evaluation.default_ops(0))
-  for batch in batches:
+  runs = [(b, on) for b in batches for on in ((False, True) if with_sections
+                                              else (False,))]
+  for batch, on in runs:
+    sections = augmentation.SectionAugmentations(SECTIONS, 1) if on else None
     trainer = trainer_lib.ConvStackTrainer(
         model, optimizer.OptimizerConfig(optimizer='momentum'),
         max_batch=batch)
@@ -93,7 +110,7 @@ def loop_part(model, volumes, coords, batches, steps):
     it = examples.BatchExampleIter(
         model.info, ops, volumes, coords, batch_size=batch,
         transform=augmentation.PermuteAndReflect((1, 2), (0, 1, 2), 1),
-        shuffle_moves=True, moves_seed=1, shuffle_seed=1,
+        shuffle_moves=True, moves_seed=1, shuffle_seed=1, sections=sections,
         io=examples.torch_io(geometry, batch, trainer.device))
 
     def run(n):
@@ -112,10 +129,11 @@ def loop_part(model, volumes, coords, batches, steps):
     t0 = time.time()
     in_step = run(steps)
     wall = time.time() - t0
-    print('  batch %2d: %6.2f steps/s, %7.1f FoVs/s (%d steps, %.3f s, %d '
+    print('  batch %2d%s: %6.2f steps/s, %7.1f FoVs/s (%d steps, %.3f s, %d '
           'examples started); train step %.2f ms; outside it %.1f %% of the '
           'wall time = %.1f us per step' % (
-              batch, steps / wall, steps * batch / wall, steps, wall,
+              batch, ' with sections' if on else '', steps / wall,
+              steps * batch / wall, steps, wall,
               it.examples_started - started, 1e3 * in_step / steps,
               100 * (1 - in_step / wall), 1e6 * (wall - in_step) / steps))
     for kind in COUNTED:
@@ -127,7 +145,22 @@ def loop_part(model, volumes, coords, batches, steps):
     trainer.close()
 
 
-def kernel_part(model, image, labels, coords, batches, repeats):
+def full_plan(g):
+  sections = g.image_patch[0]
+  plan = augmentation.SectionPlan(sections, (4, 4))
+  plan.kind, plan.z0, plan.dy, plan.dx = (augmentation.TRANSLATION,
+                                          sections // 2, 4, -4)
+  plan.blank_value = np.float32(200.0)
+  plan.blank_mask[[3, sections - 2]] = 8
+  plan.blur_sigma = np.float32(2.0)
+  plan.blur_mask[::4] = 8
+  plan.gray[:] = 1
+  plan.factors[:] = (1.1, -0.05, 0.8)
+  return plan
+
+
+def kernel_part(model, image, labels, coords, batches, repeats,
+                with_sections=False):
   ops = evaluation.default_ops(0)
   median = lambda values: float(np.median(values))
   for batch in batches:
@@ -152,6 +185,18 @@ def kernel_part(model, image, labels, coords, batches, repeats):
         times.append(ops.last_timing_train()['load_augmented'])
       rows.append(('load_augmented ' + name, median([t[0] for t in times[2:]]),
                    times[-1][1]))
+    if with_sections:
+      identity = ([(0, 1, 2)] * batch, [(0, 0, 0)] * batch)
+      for name, plan in (('empty', augmentation.SectionPlan(g.image_patch[0])),
+                         ('full', full_plan(g))):
+        times = []
+        for k in range(repeats + 2):
+          ops.load_sections(*args, *identity, [plan] * batch, 0.05)
+          times.append(ops.last_timing_sections())
+        for kind in evaluation.SECTION_CALL_KINDS:
+          rows.append(('%s %s' % (kind, name),
+                       median([t[kind][0] for t in times[2:]]),
+                       times[-1][kind][1]))
     new = lambda dims: torch.empty((batch,) + tuple(dims),
                                    dtype=torch.float32, device='cuda:0')
     io = [new(g.input_seed), new(g.input_image), new(g.pred_mask)]
@@ -182,6 +227,7 @@ def main():
   ap.add_argument('--batches', default='1,8,16')
   ap.add_argument('--kernel-batches', default='1,32')
   ap.add_argument('--repeats', type=int, default=20)
+  ap.add_argument('--sections', action='store_true')
   args = ap.parse_args()
   shape = (args.size,) * 3
   image = synthetic.cells_volume(shape, seed=1234)
@@ -195,9 +241,9 @@ def main():
   ints = lambda text: [int(b) for b in text.split(',') if b]
   print('%d^3 cells phantom, FIB-25 geometry, policy fixed' % args.size)
   loop_part(model, {'vol': (image, labels, 128.0, 33.0)}, coords,
-            ints(args.batches), args.steps)
+            ints(args.batches), args.steps, args.sections)
   kernel_part(model, image, labels, coords, ints(args.kernel_batches),
-              args.repeats)
+              args.repeats, args.sections)
 
 
 if __name__ == '__main__':

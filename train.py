@@ -31,13 +31,19 @@ A run resumes from the newest pair found in --train_dir (its example streams
 start afresh, as the reference's do).  Summaries are appended to
 <train_dir>/summaries.jsonl as JSON lines every --summary_rate_secs seconds:
 step, loss, learning rate, clipped gradient entries and the tracker's eval/*
-and moves/* summaries, which are then reset (train.py:422-423).  A loss or a
+and moves/* summaries, which are then reset (train.py:422-423).  With
+--section_augmentation (misalignment, missing section, out-of-focus section,
+grayscale perturbation of the reference's augmentation.py, on the device:
+ffn_amd/training/augmentation.py) a line also counts, since the start of the
+run, the examples, those misaligned, the sections blanked and blurred, and the
+examples perturbed, under augmentation/*.  A loss or a
 gradient that is not finite ends the run with InvalidLossError; the last
 checkpoint written stays as it is.
 
 Not here: TensorFlow-format checkpoints, replicas (--master, --task,
 --ps_tasks, --replica_step_delay), tf.train.shuffle_batch's queue (the
-coordinates are cycled, reshuffled per epoch), image summaries.  TensorFlow's
+coordinates are cycled, reshuffled per epoch), image summaries, the elastic,
+affine, rotation and tf.image contrast augmentations.  TensorFlow's
 random number streams are not reproduced: --seed makes a run of this script
 reproducible.
 """
@@ -117,6 +123,15 @@ def parse_args(argv=None):
                   'places')
   ap.add_argument('--reflectable_axes', type=_axes, default=[0, 1, 2],
                   help='subset of 0,1,2: the z, y, x axes that may be reversed')
+  ap.add_argument('--section_augmentation', type=json.loads, default=None,
+                  help='JSON arguments of the section augmentations under the '
+                  "reference's names (misalignment_skip_ratio, max_xy_offset, "
+                  'slip_vs_translate_ratio, missing_section_skip_ratio, '
+                  'max_missing_section_indices_ratio, outoffocus_skip_ratio, '
+                  'max_outoffocus_indices_ratio, max_filter_stdev, '
+                  'grayscale_skip_ratio, max_contrast_factor, '
+                  'max_brightness_factor); an augmentation whose keys are '
+                  'absent is off; default: none of them')
   # the optimizer's flags (ffn/training/optimizer.py)
   defaults = optimizer_lib.OptimizerConfig()
   ap.add_argument('--optimizer', default=defaults.optimizer,
@@ -140,6 +155,13 @@ def parse_args(argv=None):
     ap.error('--batch_size must be in [1, %d]' % evaluation.MAX_SLOTS)
   if args.checkpoint_steps < 1:
     ap.error('--checkpoint_steps must be at least 1')
+  if args.section_augmentation is not None:
+    if not isinstance(args.section_augmentation, dict):
+      ap.error('--section_augmentation takes a JSON object')
+    try:
+      augmentation.SectionAugmentations(args.section_augmentation, 0)
+    except (TypeError, ValueError) as e:
+      ap.error('--section_augmentation: %s' % e)
   return args
 
 
@@ -253,6 +275,9 @@ def write_summary(f, trainer, batches, seconds):
           'examples_finished': batches.examples_finished,
           'epochs': batches.epochs}
   line.update(batches.result.summaries())
+  if batches.sections is not None:
+    line.update({'augmentation/' + k: int(v)
+                 for k, v in batches.section_counts.items()})
   batches.reset_result()
   f.write(json.dumps({k: (float(v) if isinstance(v, np.floating) else v)
                       for k, v in line.items()}, sort_keys=True) + '\n')
@@ -283,6 +308,10 @@ def main(argv=None):
     transform = augmentation.PermuteAndReflect(
         args.permutable_axes, args.reflectable_axes,
         np.random.default_rng(seed))
+    sections = None
+    if args.section_augmentation is not None:
+      sections = augmentation.SectionAugmentations(
+          args.section_augmentation, np.random.RandomState(seed % (1 << 32)))
     ops = evaluation.default_ops(args.device)
     geometry = evaluation.Geometry.from_info(model.info, args.fov_policy,
                                              args.fov_moves, args.batch_size)
@@ -292,7 +321,7 @@ def main(argv=None):
         batch_size=args.batch_size, threshold=args.threshold,
         seed_pad=args.seed_pad, shifts=model.shifts,
         shuffle_moves=args.shuffle_moves, moves_seed=seed, transform=transform,
-        shuffle_seed=seed,
+        shuffle_seed=seed, sections=sections,
         io=examples.torch_io(geometry, args.batch_size, trainer.device))
     if batches.skipped:
       logging.info('%d coordinates skipped (patch leaves the volume)',
