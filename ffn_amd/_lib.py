@@ -19,6 +19,7 @@ CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('FFN_AMD_LIB') or os.path.join(CSRC, 'libffn_hip.so')
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'ffn_hip.h')
 HEADERS = [HEADER,
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_hip_debug.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_labels.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_seeds.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_decision.h'),
@@ -28,8 +29,9 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_optimizer.h')]
-SOURCES = ['ffn_hip.hip', 'ffn_labels.hip', 'ffn_seeds.hip', 'ffn_decision.hip',
-           'ffn_analysis.hip', 'ffn_partitions.hip', 'ffn_coordinates.hip',
+SOURCES = ['ffn_hip.hip', 'ffn_canvas.hip', 'ffn_options.hip', 'ffn_labels.hip',
+           'ffn_seeds.hip', 'ffn_decision.hip', 'ffn_analysis.hip',
+           'ffn_partitions.hip', 'ffn_coordinates.hip',
            'ffn_evaluation.hip', 'ffn_gradients.hip', 'ffn_optimizer.hip']
 
 MAX_CANDIDATES = 16
@@ -200,7 +202,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _I3 = ctypes.POINTER(ctypes.c_int32)
 
-# name -> (restype, argtypes); every symbol include/ffn_hip.h declares.
+# name -> (restype, argtypes); every symbol include/ffn_hip.h (and ffn_hip_debug.h) declares.
 SIGNATURES = {
     'ffn_abi_version': (_I, []),
     'ffn_last_error': (ctypes.c_char_p, []),

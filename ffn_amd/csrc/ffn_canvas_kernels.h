@@ -1,5 +1,5 @@
 // Canvas utility kernels: box reads / writes / fills, commit, the between-segment turn (integer / byte work, HBM-bound).
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_canvas.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {
@@ -107,7 +107,7 @@ __global__ void any_segmented_kernel(const int32_t* __restrict__ seg, Box b,
 // box narrower than a wave puts 64 >> xs rows side by side (xs: log2 of the lanes
 // a row gets, row_lanes_log2 on the host).  f(ci) is called once per voxel.
 // ---------------------------------------------------------------------------
-constexpr int kTurnBlocks = 512;    // grid cap of these sweeps = partial sums per count
+// (kTurnBlocks, the grid cap of these sweeps = partial sums per count: ffn_types.h)
 constexpr int kTurnHistLds = 4096;  // max_existing_id + 1 <= this: overlaps counted in LDS
 
 template <typename F>
@@ -213,12 +213,7 @@ __global__ void commit_assign_kernel(const float* __restrict__ seed,
 // publish), no memset, no copy operation, no stream wait.  Phases that depend on
 // each other are separate launches: no workgroup waits for another.
 // ---------------------------------------------------------------------------
-struct TurnRecord {
-  unsigned long long counts[2];  // raw, actual (turn_count_kernel's partials, summed)
-  int committed;                 // the id was assigned
-  int chosen;                    // index of the next seed in the candidate list, -1 none
-  int pad[2];
-};
+// (the record of a turn, TurnRecord: ffn_types.h)
 constexpr int kTurnOk = 0, kTurnSegmented = 1, kTurnTooClose = 2, kTurnNotReached = 3,
               kTurnRestricted = 4;
 

@@ -1,5 +1,5 @@
 // The exact-f32 3x3x3 32->32 convs (conv_variant 0 and 2): v_mfma_f32_16x16x4_f32, bitwise the oracle's fmaf chain.
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {

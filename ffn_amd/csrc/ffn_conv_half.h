@@ -1,6 +1,6 @@
 // conv32h / conv32hs: the split-product conv on 16-position tiles, 80-voxel workgroups -- two
 // independent hand-off chains per SIMD inside ONE FoV (conv_variant 10; measured, not the default).
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {

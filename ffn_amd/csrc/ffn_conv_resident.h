@@ -1,5 +1,5 @@
 // conv32ps: the conv stack of a single-FoV step as ONE resident launch (engine option flow = 2).
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {

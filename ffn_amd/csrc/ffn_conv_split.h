@@ -1,5 +1,5 @@
 // The split-product 3x3x3 32->32 convs (conv_variant 6 .. 9: conv32d, conv32m, conv32mt), their FLOW hand-off and the helpers they share.
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {
@@ -115,8 +115,6 @@ struct ConvDArgs {
                          // behind the poll; 4 buffer_wbl2 sc1 in front of the publish
 };
 
-constexpr int kDbgMaxWgs = 4096;
-
 // dense index v of this layout -> index in the caller's dense [z][y][x] order
 // (logits, seed_raw); the identity unless the axes are permuted
 __device__ __forceinline__ int caller_index(const ConvDArgs& a, int v) {
@@ -169,7 +167,6 @@ __device__ __forceinline__ void stamp_workgroup(const ConvDArgs& a, const ConvLa
 // the step through the range flag (the host repeats it without FLOW).
 // ---------------------------------------------------------------------------
 constexpr unsigned kFlowSpinMax = 1u << 15;
-constexpr int kFlowTraceLayers = 64;
 // FFN_EXPERIMENTS (tools/build_variant.sh exp -DFFN_EXPERIMENTS=1): the arms the
 // rounds' A/B runs selected through engine option flow_debug (bits 1, 2, 4, 32,
 // 64, 1024, the sleep selector in bits 8-9) and the debug_clock 4 stamps of

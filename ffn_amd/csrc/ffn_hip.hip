@@ -4,6 +4,11 @@
 // activation buffers for up to max_batch concurrent fields of view.  Canvases
 // (image / seed / segmentation of a whole subvolume) are device resident.
 // The reference interfaces each entry point replaces are cited in the header.
+//
+// This unit: the engine itself (create, destroy, weights, the pace tuner), every conv
+// launcher and run_stack, the stateless predict calls, the FoV step (submit, wait) and
+// the segment loop that drives it.  What a canvas does between steps is ffn_canvas.hip;
+// options, profiler and debug readers are ffn_options.hip (ffn_engine.h).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -13,36 +18,22 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "ffn_internal.h"
+#include "ffn_engine.h"
 #include "ffn_kernels.h"
-#include "ffn_restrict_kernels.h"
-#include "ffn_host_loop.h"
-
-using namespace ffn;
+#include "ffn_step_kernels.h"
+#include "ffn_conv_exact.h"
+#include "ffn_conv_split.h"
+#include "ffn_conv_resident.h"
+#include "ffn_conv_half.h"
 
 namespace {
-
-constexpr int kHeadBlocks = 281;  // head kernel grid.x (4 sweeps of 32 voxels x 281)
-
 thread_local std::string g_error;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_error = buf;
-  return code;
-}
-
 }  // namespace
 
 int ffn_set_error(int code, const char* fmt, ...) {
@@ -56,337 +47,6 @@ int ffn_set_error(int code, const char* fmt, ...) {
 }
 
 namespace {
-
-#define HIP_TRY(expr)                                                        \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess)                                                    \
-      return fail(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,               \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                \
-  } while (0)
-
-}  // namespace
-
-struct ffn_engine {
-  // Entry points may be called from several host threads (the two canvas groups
-  // of MultiCanvasDriver, their between-segment work): each one holds this lock
-  // while it touches engine state or queues work on the stream -- except the
-  // wait for a step's completion flags, which is what the threads overlap.
-  std::recursive_mutex mu;
-  // The canvas utility calls (point / box reads and writes, commit counts) own
-  // the scratch buffers and WAIT for their result; they hold `util_mu` for all
-  // of it but `mu` only while they queue their work, and wait for their own
-  // event, not for the stream -- so another thread's next FoV step is queued
-  // (and runs) behind them instead of waiting for the host to wake up.
-  std::mutex util_mu;
-  // They run on their OWN stream: a canvas between two segments is in no step,
-  // so what is committed / read / re-seeded on it must not queue behind the FoV
-  // steps other canvases have in flight (2 ms each at batch 16).  Ordering
-  // per canvas: the step side waits for the canvas' last utility event
-  // (ffn_canvas::ev_util) before its next step; the utility side starts after
-  // the canvas' last step has pasted -- batched steps paste BEFORE the faces
-  // kernel raises the completion flag the host waits for, a single-FoV step
-  // (faces first: the host's turn-around is on its critical path) makes the
-  // utility stream wait for an event recorded behind it.
-  hipStream_t ustream = nullptr;
-  hipEvent_t main_ev = nullptr;  // "everything queued on `stream` so far"
-  // ffn_canvas_segment_many_carry: the batched step it left in flight when it
-  // returned (one per engine: the driver that runs ONE group of canvases and
-  // does a canvas' between-segment work under the others' next step).  `many_mu`
-  // is taken before `mu`, never the other way round.
-  std::mutex many_mu;
-  ffn_host::ManyCarry many_carry;
-  uint32_t many_ticket = 0;
-  std::vector<ffn_canvas*> many_canvases;  // the carried step's, in batch order
-  int device = 0;
-  hipStream_t stream = nullptr;
-  Geom g{};   // the FoV as the caller sees it (zyx): gather / paste / faces, I/O
-  Geom gp{};  // the FoV as the split-product kernels (conv_variant >= 6) lay it
-              // out: the same, or with its axes permuted (oa) so that the
-              // SHORTEST axis is the row direction -- rows of 21 instead of 41
-              // voxels put the anisotropic 21 x 41 x 41 FoV inside the row
-              // budget of conv32m / conv32mt
-  bool permuted = false;
-  int depth = 0;
-  int max_batch = 0;
-  bool weights_set = false;
-
-  float* act_base = nullptr;  // 2 activation buffers (T, X) x max_batch
-  float* bufT = nullptr;      // logical origins
-  float* bufX = nullptr;
-  uint32_t* validbits = nullptr;
-  int32_t* pidx = nullptr;    // dense FoV index -> padded position (variant 2)
-  int nchunks_c = 0, Rc = 0;
-  int fuse_head = 1;      // 1x1x1 head fused into the last conv32c launch
-  int count_blocks = kHeadBlocks;  // entries per item in `count` for the last step
-  int store_policy = 1;  // conv32c epilogue stores: sc1 write-through (-1.4 % per stack)
-  long long* d_dbg = nullptr;  // debug clocks of conv32c WG 0 (24 values)
-  int dbg_clock = 0;
-  int dbg_layer = 3;      // the launch whose clocks are recorded (3 = a conv_a)
-  size_t lds_bytes_c = 0;
-  // conv32d (variant 6): 160-voxel chunks, the 27 taps split over the waves,
-  // split-plane activations, LDS-DMA staging
-  int nchunks_k = 0, Rc_k = 0;
-  bool k_ok = false;             // the chunk + halo fits the LDS slots
-  // rawT / rawX / rawS: the three activation allocations
-  float* rawT = nullptr;
-  float* rawX = nullptr;
-  float* rawS = nullptr;
-  bool d_ok = false;
-  // conv32d with 96-voxel chunks, two workgroups per CU (variant 7)
-  bool e_ok = false;
-  int batch_chunks = 1;   // option: variant 6 uses the 96-voxel form for n >= 2
-  bool small_now = false; // the stack being queued uses the 96-voxel form
-  // conv32m (variant 8): M split over the waves, weights through an LDS ring
-  bool m_ok = false;
-  bool m_now = false;
-  // conv32mt (variant 9): conv32m for the first n_main <= 256 chunks, 32-voxel
-  // K-split tail workgroups for the rest
-  bool t_ok = false;
-  bool t_now = false;
-  int tail_batched = 0;  // option: steps with >= 2 FoVs take the tail form too
-  // FLOW (ffn_conv_split.h "flagged launches"): 0 off; 1 conv32mt's launches with
-  // the flagged hand-off compiled in (still one dependent launch per conv: the
-  // words are always there already -- isolates the cost of the sc1 reads and
-  // the poll); 2 the resident stack, conv32ps: ONE launch for the 2 depth - 1 convs
-  // of a single-FoV step
-  int flow = 0;
-  unsigned* flow_flags = nullptr;  // one word per producer workgroup, kFlowStride apart
-  unsigned* flow_err = nullptr;    // polls that gave up, ever
-  unsigned flow_epoch = 0;         // sequence number of the last conv queued
-  int flow_debug = 0;              // debug option: ConvDArgs::flow_dbg
-  // The resident launch needs every one of its workgroups on the chip at once.
-  // flow_fits: the device can hold them (CU count x occupancy, checked at create);
-  // at run time a poll that gives up voids the step (FFN_ERR_FLOW): the repeat
-  // runs per-layer launches (flow_skip, one stack), and kFlowStrikes voided
-  // resident steps in a row turn the resident launch off for this engine
-  // (flow_auto_off; option "flow" turns it on again).
-  bool flow_fits = false;
-  int flow_strikes = 0;            // voided resident steps since the last good one
-  int flow_skip = 0;               // the next single-FoV stack runs per-layer launches
-  int flow_auto_off = 0;
-  long stat_flow_voids = 0;
-  bool last_stack_resident = false;  // what run_stack queued last
-  bool slot_resident[2] = {false, false};
-  long long* flow_trace = nullptr; // debug_clock 4: ConvDArgs::flow_trace
-  int flow_trace_slots = 0;
-  int n_main = 0, n_tail = 0, n_tail3 = 0;  // tail workgroups of 32 / 96 voxels
-  int tsched_aoff[4 * 8] = {};
-  int t3sched_aoff[4 * 8] = {};
-  int nchunks_m = 0;
-  int nchunks_e = 0;
-  size_t lds_bytes_e = 0;
-  int esched_aoff[4 * 8] = {};
-  bool d_weights_ok = true;      // every |weight| x 2^11 inside the fp16 range
-  uint16_t* wpackd = nullptr;    // [28][khalf][plane hi, res][64][8] fp16 per layer
-  size_t wpackd_layer = 0;       // halves per layer
-  // conv32h / conv32hs (variant 10): 80-voxel workgroups on 16x16x32 tiles, two
-  // hand-off chains per SIMD for a single FoV; several FoVs run conv32m as under 9
-  uint16_t* wpackh = nullptr;    // [28][out half][plane hi, res][64][8] fp16 per layer
-  bool h_ok = false;             // geometry + residency
-  bool h_now = false;            // the stack being queued is conv32h's
-  int n_half = 0;                // 80-voxel chunks of the FoV
-  // Pacing of the resident stack (ConvStackTab::pace, 10-ns ticks between two convs of a
-  // workgroup).  flow_pace: -1 = the beat measured by tune_pace() when the weights were
-  // set (conv_variant 9; 0 if no beat beat the free-running stack), 0 = off, > 0 = that
-  // beat.  flow_pace_spread: -1 = as wide as the beat (the FoV's last voxel one beat behind
-  // its first), else ticks.
-  int flow_pace = -1;
-  int flow_pace_tail = 0;        // ConvStackTab::pace_tail
-  int flow_pace_spread = -1;
-  int pace_auto = 0;             // tune_pace()'s beat (0: none)
-  float pace_auto_us[2] = {0.f, 0.f};  // us per stack it measured: free-running, at the beat
-  int cus = 0;                   // compute units of the device
-  size_t lds_bytes_d = 0;        // 3 slots x 8 planes x Rc_k rows x 16 B
-  int dsched_aoff[4 * 8] = {};
-  int dsched_btap[4 * 8] = {};
-  unsigned* range_flag = nullptr;  // device word: tag of the last void run
-  // Speculative conv0_a of a single-FoV step's successor (SpecArgs): the launch
-  // queued behind the last step's paste, and what a step must match to run on it
-  struct Spec {
-    bool valid = false;
-    const ffn_canvas* canvas = nullptr;
-    int n = 0;
-    int pos[kSpecMax][3] = {};
-    float pad_value = 0.f, move_thr = 0.f;
-    int variant = 0;
-  } spec;
-  int speculate = 1;        // option
-  int spec_force_mismatch = 0;  // debug option: fail the next N matches
-  long stat_spec_mismatch = 0;
-  long stat_many_carried = 0;  // batched steps left in flight across a return
-  int fuse_paste = 1;       // option: faces + paste of a single FoV as one launch
-  int fuse_conv0a = 1;      // option: ... and the next step's conv0_a in it as well
-  int* d_spec_choice = nullptr;
-  long stat_spec_launched = 0, stat_spec_hits = 0;
-  long stat_spec_miss_full = 0, stat_spec_miss_short = 0;
-  // ffn_canvas_segment_turn on the host: queueing its sequence, waiting for its record
-  long long stat_segturn_queue_ns = 0, stat_segturn_wait_ns = 0;
-  long stat_segturn_calls = 0;
-  // The NEXT step's resident stack queued right behind the launch that holds its
-  // speculative conv0_a, before the host has seen this step's record (engine option
-  // stack_ahead): the stack reads only what that conv0_a wrote (and gives up after its
-  // first conv when the device found no valid position), so the host's turn-around and
-  // the launch latency of the stack leave the step's critical path.
-  int stack_ahead = 1;
-  int paste_blocks = 0;  // fused step launch: paste blocks (0: one block per CU, see kPasteBlocks)
-  int debug_submit_delay_ns = 0;
-  int debug_fused_twice = 0;  // experiment: the host idles this long in front of a step's launches
-  bool trace_now = false;     // debug_fused_trace: the launches being queued stamp
-  bool ahead_valid = false;   // such a stack is in the stream, for the step e->spec describes
-  long stat_ahead_used = 0, stat_ahead_wasted = 0;
-  unsigned range_tag = 0;        // tag of the run being queued
-  bool fp16_ok = true;           // every weight inside the fp16 range
-  int conv_variant = 0;       // 0 conv32 (any FoV), 2 conv32c (exact f32), 6 conv32d, 7 = 6
-                              // with 96-voxel chunks, 8 conv32m, 9 conv32mt (+ conv32m)
-  int exact_variant = 0;      // the f32 kernel a voided fp16 step is repeated with: 2
-                              // where conv32c takes the FoV, else 0
-  float* h_io = nullptr;      // pinned staging of ffn_predict: seed, image, logits
-  float* up_image = nullptr;  // dense FoVs uploaded by ffn_predict
-  float* up_seed = nullptr;
-  float* seed_raw = nullptr;  // raw (NaN-preserving) seed FoV of the current step
-  // The conv0_a of the NEXT step may run in the same launch as this step's faces
-  // and paste (faces_paste_conv0a_kernel): what it writes -- the raw seed copy,
-  // a range flag, the position it chose -- goes to the OTHER of two sets, which
-  // run_stack makes the current one when that step is queued.
-  float* seed_raw_alt = nullptr;
-  unsigned* range_flag_alt = nullptr;
-  int* d_spec_choice_alt = nullptr;
-  float* logits = nullptr;
-  unsigned* count = nullptr;
-  uint8_t* valid = nullptr;
-  float* weights = nullptr;  // one allocation; layout below
-  size_t w0a_off = 0, b0a_off = 0, wl_off = 0;
-  size_t w0ap_off = 0;  // conv0_a weights with the taps in gp's axis order
-  std::vector<size_t> wpack_off, bias_off;  // 2*depth-1 entries (conv0_b ..)
-
-  StepItem* d_items = nullptr;
-  StepItem* h_items = nullptr;
-  // pinned, written by the faces block: kPubWords 8-byte words per item and slot,
-  // (step number << 32) | one 32-bit word of the item's ffn_step_result
-  unsigned long long* h_pub = nullptr;
-  unsigned step_id = 0;
-  // two result / descriptor slots: one step may be queued behind the running one
-  int next_slot = 0;
-  int slot_n[2] = {0, 0};
-  bool slot_waited[2] = {false, false};  // a thread is in ffn_canvas_step_wait for it
-  unsigned slot_ticket[2] = {0, 0};
-  std::vector<ffn_canvas*> slot_canvas[2];
-  int sync_mode = 1;  // 0 = hipStreamSynchronize, 1 = poll h_pub (then sync)
-  // since the last set_option("stat_reset"): batched step calls, FoVs in them,
-  // and a histogram of FoVs per call (index min(n, 64))
-  long stat_calls = 0, stat_items = 0;
-  long stat_hist[65] = {};
-  // the turn-around between two single-FoV steps: the GPU's view (d_stamps, see
-  // ConvStackTab::stamps) and the host's (steady-clock ns from "record arrived" to
-  // "the next resident launch is queued", and inside that hipLaunchKernelGGL alone)
-  long long* d_stamps = nullptr;
-  long long t_arrived_ns = 0;
-  int fused_trace_in = 0;        // debug_fused_trace: steps until the traced one
-  long long stat_turn_host_ns = 0, stat_launch_host_ns = 0;
-  long stat_turn_host_count = 0;
-
-  void* d_scratch = nullptr;
-  void* h_scratch = nullptr;
-  size_t scratch_bytes = 0;
-
-  // The segment turn's own scratch (ffn_canvas_segment_turn, ffn_canvas_commit_count;
-  // under util_mu, on the utility stream).  d_turn: [TurnRecord][partials: kTurnBlocks
-  // pairs][flags, seed, seg: 4 bytes, voxel index: 8 bytes, turn_ncap each][histogram:
-  // turn_hcap words].  The histogram is zeroed when it is allocated and every turn's
-  // last kernel leaves it zero again (turn_hist_clean: false while a turn is under way
-  // or after one that failed -- the next one zeroes it first).  h_turn: pinned and
-  // device-mapped, 8-byte words: [candidates, 3 turn_ncap int32][published: 8 +
-  // 3 turn_ncap + 2 turn_ocap words, upper half = turn_seq of the turn that wrote it].
-  void* d_turn = nullptr;
-  unsigned long long* h_turn = nullptr;
-  unsigned long long* h_turn_dev = nullptr;  // h_turn as the device addresses it
-  size_t turn_ncap = 0, turn_hcap = 0, turn_ocap = 0;
-  bool turn_hist_clean = false;
-  unsigned turn_seq = 0;
-
-  int prof_mode = 0;
-  std::vector<hipEvent_t> events;
-  int events_used = 0;
-  // the event pair around a stack queued AHEAD (stack_ahead): it joins the samples when the
-  // stack is used by its step -- one that found no position to run at ends after its first
-  // conv, and its ~10 us would pass for a stack's duration
-  hipEvent_t ahead_ev[2] = {nullptr, nullptr};
-  bool ahead_ev_pending = false;
-  double conv_ms = 0.0;
-  int64_t conv_launches = 0;
-  size_t lds_bytes = 0;
-  std::vector<ffn_canvas*> canvases;  // live canvases created from this engine
-  int prof_every = 1;                 // profile 1 of every N run_stack calls
-  long stack_calls = 0;
-  bool prof_now = false;
-  int ablate = 0;                     // debug: skip phases of the conv kernel
-  std::vector<int> chain_launches_pending;  // mode 2: launches per event pair
-  std::vector<float> prof_samples;  // ms of every event pair since the last reset
-};
-
-struct ffn_canvas {
-  ffn_engine* engine = nullptr;
-  float* image = nullptr;        // f32 image; NULL for a uint8 canvas
-  uint8_t* image_u8 = nullptr;   // uint8 canvas: raw image (1 B / voxel) ...
-  float* image_lut = nullptr;    // ... and (v - mean) / stddev for v = 0..255
-  float* seed = nullptr;
-  int32_t* seg = nullptr;
-  int cz = 0, cy = 0, cx = 0;
-  size_t nvox = 0;
-  // Bounding box of every seed voxel that may differ from NaN since the last
-  // clear: Canvas.init_seed (inference.py:443-450) clears the WHOLE volume per
-  // seed (62.5 MB at 250^3, 4.3 GB at 1024^3); here only this box is re-filled.
-  int dirty_lo[3] = {0, 0, 0};
-  int dirty_hi[3] = {0, 0, 0};  // exclusive; lo >= hi: nothing dirty
-  ffn_host::SegmentState loop;  // ffn_canvas_segment_at's queue / visited set
-  hipEvent_t ev_util = nullptr;  // behind the last utility operation on this canvas
-  bool util_pending = false;     // ... which the next step has to wait for
-  bool paste_after_flag = false; // the last step pasted AFTER raising its flag
-  // the segment loop's guess of the positions the step after the next one may
-  // be made at (consumed by the next single-FoV ffn_canvas_step_submit)
-  int hint_n = 0;
-  int hint_pos[kSpecMax][3] = {};
-  bool hint_from_loop = false;  // the next step is the segment loop's own
-  // MovementRestrictor (ffn_canvas_set_restrictor): [pos plane][seed plane] of
-  // restrict_plane_words 64-bit words each (ffn_restrict_kernels.h); NULL: none.
-  // The host loop reads its copy of the pos plane (restrict_host).
-  unsigned long long* restrict_planes = nullptr;
-  size_t restrict_plane_words = 0;
-  int restrict_row_words = 0;
-  std::vector<uint64_t> restrict_host;
-
-  void mark_dirty(const int lo[3], const int hi[3]) {
-    const int dims[3] = {cz, cy, cx};
-    const bool empty = dirty_lo[0] >= dirty_hi[0];
-    for (int k = 0; k < 3; ++k) {
-      const int l = std::max(lo[k], 0), h = std::min(hi[k], dims[k]);
-      dirty_lo[k] = empty ? l : std::min(dirty_lo[k], l);
-      dirty_hi[k] = empty ? h : std::max(dirty_hi[k], h);
-    }
-  }
-};
-
-namespace {
-inline long long steady_ns() {
-  return std::chrono::duration_cast<std::chrono::nanoseconds>(
-             std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-inline unsigned next_tag(unsigned t) { return t + 1 ? t + 1 : 1; }  // never 0
-// A speculative conv0_a launch that no step will use: its range tag is spent.
-inline void drop_spec(ffn_engine* e) {
-  if (e->spec.valid && !e->ahead_valid) e->range_tag = next_tag(e->range_tag);
-  // (a stack queued ahead has taken the tag already: run_stack)
-  if (e->ahead_valid) e->stat_ahead_wasted += 1;
-  e->spec.valid = false;
-  e->ahead_valid = false;
-}
-struct EngineLock {
-  std::unique_lock<std::recursive_mutex> lk;
-  explicit EngineLock(ffn_engine* e) {
-    if (e) lk = std::unique_lock<std::recursive_mutex>(e->mu);
-  }
-};
 constexpr int kFlowStrikes = 3;
 
 // A step came back void, and its own record says why (ffn_step_result.range_error
@@ -419,227 +79,6 @@ int flow_voided(ffn_engine* e, bool timed_out) {
               "workgroups: the step changed nothing; repeat it (the repeat runs one "
               "launch per conv, same arithmetic)");
 }
-
-// util_mu, then mu (the step path takes only mu: no lock-order inversion)
-struct UtilLock {
-  std::unique_lock<std::mutex> ul;
-  std::unique_lock<std::recursive_mutex> lk;
-  explicit UtilLock(ffn_engine* e) {
-    if (e) {
-      ul = std::unique_lock<std::mutex>(e->util_mu);
-      lk = std::unique_lock<std::recursive_mutex>(e->mu);
-    }
-  }
-  // Before the first utility operation of a call: the canvas' last step has
-  // pasted (see ffn_engine::ustream).
-  // reads_only: the call looks at the canvas and changes nothing -- a speculative conv0_a
-  // (and the stack queued behind it) stays what it is; the segment loop's own point reads
-  // between two steps used to cost it its launch (0.5 % of the steps: a whole stack run for
-  // nothing + a step made the ordinary way)
-  hipError_t begin(ffn_engine* e, ffn_canvas* c, bool reads_only = false) {
-    if (!reads_only) drop_spec(e);  // the canvas may change under a speculative conv0_a
-    if (!c->paste_after_flag) return hipSuccess;
-    hipError_t err = hipEventRecord(e->main_ev, e->stream);
-    if (err == hipSuccess) err = hipStreamWaitEvent(e->ustream, e->main_ev, 0);
-    if (err == hipSuccess) c->paste_after_flag = false;
-    return err;
-  }
-  // After the last one: mark the point the canvas' next step waits for ...
-  hipError_t end(ffn_engine* e, ffn_canvas* c) {
-    c->util_pending = true;
-    return hipEventRecord(c->ev_util, e->ustream);
-  }
-  // ... and, for calls that return data, wait for it (`mu` released meanwhile)
-  hipError_t wait(ffn_engine* e, ffn_canvas* c) {
-    hipError_t err = end(e, c);
-    if (err != hipSuccess) return err;
-    lk.unlock();
-    err = hipEventSynchronize(c->ev_util);
-    lk.lock();
-    if (err == hipSuccess) c->util_pending = false;  // done: nothing to wait for
-    return err;
-  }
-  // ... or, where the call's last kernel publishes what the call returns into pinned
-  // memory (turn_publish_kernel), poll for it instead of blocking on the stream (`mu`
-  // released meanwhile).  arrived(): every published word carries this call's number.
-  // Bounded, and as ffn_canvas_step_wait polls: no hipStreamQuery in the loop (on a busy
-  // stream it puts a barrier packet into the queue), the stream is asked only after 2 ms
-  // without the record, then every 2 ms, so that a device fault still surfaces as an error.
-  // That last kernel runs behind everything the call queued, so the canvas is left as a
-  // completed wait() leaves it: nothing pending, and ev_util -- not recorded again here --
-  // complete, since whatever recorded it last ran earlier on the same stream.
-  template <typename Arrived>
-  hipError_t wait_published(ffn_engine* e, ffn_canvas* c, Arrived arrived) {
-    if (e->sync_mode != 1) {
-      const hipError_t err = wait(e, c);
-      if (err != hipSuccess) return err;
-      return arrived() ? hipSuccess : hipErrorUnknown;
-    }
-    lk.unlock();
-    bool done = false;
-    long long t_first = 0, t_query = 0;
-    for (long spin = 0; !done; ++spin) {
-      done = arrived();
-      if (!done && (spin & 0xfff) == 0xfff) {
-        const long long now = steady_ns();
-        if (t_first == 0) t_first = t_query = now;
-        if (now - t_first > 10000000000LL) break;  // 10 s: let the stream say what happened
-        if (now - t_query > 2000000) {
-          t_query = now;
-          if (hipStreamQuery(e->ustream) != hipErrorNotReady) break;  // drained, or an error
-        }
-      }
-    }
-    hipError_t err = hipSuccess;
-    if (!done) {
-      err = hipStreamSynchronize(e->ustream);
-      if (err == hipSuccess && !arrived()) err = hipErrorUnknown;  // the kernel died
-    }
-    lk.lock();
-    if (err == hipSuccess) c->util_pending = false;
-    return err;
-  }
-};
-// host-side: nothing queued on canvas c is still running
-hipError_t canvas_quiesce(ffn_engine* e, ffn_canvas* c) {
-  drop_spec(e);  // the caller is about to read or change the canvas directly
-  hipError_t err = hipSuccess;
-  if (c->paste_after_flag) {
-    err = hipStreamSynchronize(e->stream);
-    if (err == hipSuccess) c->paste_after_flag = false;
-  }
-  if (err == hipSuccess && c->util_pending) {
-    err = hipEventSynchronize(c->ev_util);
-    if (err == hipSuccess) c->util_pending = false;
-  }
-  return err;
-}
-}  // namespace
-
-int ffn_canvas_view(ffn_canvas* c, FfnCanvasView* out) {
-  if (!c || !out) return ffn_set_error(FFN_ERR_ARG, "NULL canvas");
-  if (!c->engine)
-    return ffn_set_error(FFN_ERR_STATE, "canvas outlived its engine");
-  {
-    // the caller (label / seed kernels on their own streams) reads the canvas
-    // once the engine's stream is idle: the utility stream has to be, too
-    EngineLock lock_(c->engine);
-    if (canvas_quiesce(c->engine, c) != hipSuccess)
-      return ffn_set_error(FFN_ERR_HIP, "canvas_quiesce failed");
-  }
-  out->device_id = c->engine->device;
-  out->engine_stream = c->engine->stream;
-  out->image = c->image;
-  out->image_u8 = c->image_u8;
-  out->image_lut = c->image_lut;
-  out->segmentation = c->seg;
-  out->shape_zyx[0] = c->cz;
-  out->shape_zyx[1] = c->cy;
-  out->shape_zyx[2] = c->cx;
-  return FFN_OK;
-}
-
-namespace {
-
-int ensure_scratch(ffn_engine* e, size_t bytes) {
-  if (bytes <= e->scratch_bytes) return FFN_OK;
-  HIP_TRY(hipStreamSynchronize(e->ustream));  // (only utility calls use it)
-  if (e->d_scratch) HIP_TRY(hipFree(e->d_scratch));
-  if (e->h_scratch) HIP_TRY(hipHostFree(e->h_scratch));
-  e->d_scratch = e->h_scratch = nullptr;
-  e->scratch_bytes = 0;
-  size_t want = std::max<size_t>(bytes, 1 << 20);
-  HIP_TRY(hipMalloc(&e->d_scratch, want));
-  HIP_TRY(hipHostMalloc(&e->h_scratch, want, hipHostMallocDefault));
-  e->scratch_bytes = want;
-  return FFN_OK;
-}
-
-// ffn_engine::d_turn / h_turn for n candidates, a histogram of hist_n bins and
-// up to novl published overlap pairs
-struct TurnLayout {
-  size_t o_part, o_flag, o_hist, d_bytes;  // d_turn, bytes
-  size_t w_pub, h_words;                   // h_turn, 8-byte words
-  TurnLayout(size_t ncap, size_t hcap, size_t ocap) {
-    o_part = sizeof(TurnRecord);
-    o_flag = o_part + (size_t)kTurnBlocks * 16;
-    o_hist = o_flag + 20 * ncap;
-    d_bytes = o_hist + 4 * hcap;
-    w_pub = 3 * ncap / 2;
-    h_words = w_pub + 8 + 3 * ncap + 2 * ocap;
-  }
-};
-
-int ensure_turn(ffn_engine* e, size_t n, size_t hist_n, size_t novl) {
-  if (n > e->turn_ncap || hist_n > e->turn_hcap || novl > e->turn_ocap) {
-    HIP_TRY(hipStreamSynchronize(e->ustream));  // (only utility calls use it)
-    if (e->d_turn) HIP_TRY(hipFree(e->d_turn));
-    if (e->h_turn) HIP_TRY(hipHostFree(e->h_turn));
-    e->d_turn = nullptr;
-    e->h_turn = e->h_turn_dev = nullptr;
-    const size_t ncap = (std::max<size_t>({n, e->turn_ncap, 256}) + 3) & ~(size_t)3;
-    const size_t hcap = std::max<size_t>({hist_n, e->turn_hcap, (size_t)kTurnHistLds});
-    const size_t ocap = std::max<size_t>({novl, e->turn_ocap, 1024});
-    e->turn_ncap = e->turn_hcap = e->turn_ocap = 0;
-    const TurnLayout lay(ncap, hcap, ocap);
-    HIP_TRY(hipMalloc(&e->d_turn, lay.d_bytes));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->h_turn), lay.h_words * 8,
-                          hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(e->h_turn, 0, lay.h_words * 8);  // no word carries a live turn's number
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&e->h_turn_dev), e->h_turn, 0));
-    e->turn_ncap = ncap;
-    e->turn_hcap = hcap;
-    e->turn_ocap = ocap;
-    e->turn_hist_clean = false;
-  }
-  if (!e->turn_hist_clean) {
-    // newly allocated, grown, or left behind by a turn that failed: zeroed here, once
-    const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
-    HIP_TRY(hipMemsetAsync(static_cast<char*>(e->d_turn) + lay.o_hist, 0,
-                           4 * e->turn_hcap, e->ustream));
-  }
-  e->turn_hist_clean = false;  // until this turn's publish kernel has run
-  return FFN_OK;
-}
-
-// for_box_rows: log2 of the lanes a row of nx voxels gets (1 .. 64 of them)
-int row_lanes_log2(int nx) {
-  int xs = 0;
-  while (xs < 6 && (1 << xs) < nx) ++xs;
-  return xs;
-}
-
-// the grid of a for_box_rows sweep: 4 waves per block, 64 >> xs rows per wave pass
-int turn_grid(long rows, int xs) {
-  const long per_block = 4 * (64 >> xs);
-  return (int)std::max<long>(1, std::min<long>((rows + per_block - 1) / per_block,
-                                               kTurnBlocks));
-}
-
-// What turn_publish_kernel wrote for call `seq`, n candidates: words whose upper half
-// is seq have arrived (see the kernel for the layout).
-struct TurnPub {
-  const unsigned long long* w;
-  unsigned seq;
-  size_t n;
-  uint32_t at(size_t k) const { return (uint32_t)__atomic_load_n(&w[k], __ATOMIC_RELAXED); }
-  bool has(size_t first, size_t count) const {
-    for (size_t k = first; k < first + count; ++k)
-      if ((unsigned)(__atomic_load_n(&w[k], __ATOMIC_ACQUIRE) >> 32) != seq) return false;
-    return true;
-  }
-  // the header says how many pairs follow the candidates' words
-  bool arrived() const { return has(0, 8 + 3 * n) && has(8 + 3 * n, 2 * (size_t)at(7)); }
-  // into the caller's arrays; returns the exact number of overlapped ids
-  int overlaps(int32_t* ids, int64_t* counts) const {
-    const size_t o = 8 + 3 * n;
-    for (size_t k = 0; k < at(7); ++k) {
-      ids[k] = (int32_t)at(o + 2 * k);
-      counts[k] = (int64_t)at(o + 2 * k + 1);
-    }
-    return (int)at(6);
-  }
-};
 
 template <bool RI, bool RO, bool SK>
 int set_lds_attr(size_t bytes) {
@@ -765,25 +204,6 @@ int set_lds_attr_c(size_t bytes) {
   return FFN_OK;
 }
 
-// Flush the per-launch event pairs recorded since the last flush.
-int flush_events(ffn_engine* e) {
-  if (e->events_used == 0) return FFN_OK;
-  HIP_TRY(hipEventSynchronize(e->events[e->events_used - 1]));
-  for (int k = 0; k + 1 < e->events_used; k += 2) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e->events[k], e->events[k + 1]));
-    e->conv_ms += ms;
-    if (e->prof_samples.size() < (size_t)(1 << 16)) e->prof_samples.push_back(ms);
-    if (e->prof_mode == 2 && !e->chain_launches_pending.empty()) {
-      e->conv_launches += e->chain_launches_pending.front();
-      e->chain_launches_pending.erase(e->chain_launches_pending.begin());
-    } else {
-      e->conv_launches += 1;
-    }
-  }
-  e->events_used = 0;
-  return FFN_OK;
-}
 
 template <bool RI, bool RO, bool SK>
 int launch_conv32(ffn_engine* e, int n, const float* in, float* out,
@@ -900,6 +320,9 @@ int launch_conv32c(ffn_engine* e, int n, const float* in, float* out,
 
 // The split-plane layout of variant 6 and the f32 layout of the others keep their
 // zero padding in different bytes of the same allocations: re-zero on a change.
+// (declared in ffn_engine.h: the option setter calls it too)
+}  // namespace
+
 int switch_variant(ffn_engine* e, int value) {
   if ((value >= 6) != (e->conv_variant >= 6)) {
     HIP_TRY(hipSetDevice(e->device));
@@ -910,6 +333,8 @@ int switch_variant(ffn_engine* e, int value) {
   e->conv_variant = value;
   return FFN_OK;
 }
+
+namespace {
 
 // conv32d launch: KIND 0 conv_a (T' = split(relu(conv(X') + b))), KIND 1 conv_b
 // (X = conv(T') + b [+ X]; X' = split(relu(X))), or the fused head
@@ -1434,39 +859,6 @@ int dense_items(ffn_engine* e, int n, StepItems* si) {
     HIP_TRY(hipMemcpyAsync(e->d_items, e->h_items, sizeof(StepItem) * n,
                            hipMemcpyHostToDevice, e->stream));
   return FFN_OK;
-}
-
-Box make_box(const ffn_canvas* c, const int32_t lo[3], const int32_t hi[3],
-             long* total) {
-  Box b;
-  for (int k = 0; k < 3; ++k) {
-    b.lo[k] = lo[k];
-    b.n[k] = hi[k] - lo[k];
-  }
-  b.cy = c->cy;
-  b.cx = c->cx;
-  *total = (long)b.n[0] * b.n[1] * b.n[2];
-  return b;
-}
-
-int check_canvas(const ffn_canvas* c) {
-  if (!c) return fail(FFN_ERR_ARG, "null canvas");
-  if (!c->engine) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  return FFN_OK;
-}
-
-int check_box(const ffn_canvas* c, const int32_t lo[3], const int32_t hi[3]) {
-  const int dims[3] = {c->cz, c->cy, c->cx};
-  for (int k = 0; k < 3; ++k)
-    if (lo[k] < 0 || hi[k] > dims[k] || hi[k] < lo[k])
-      return fail(FFN_ERR_ARG, "box [%d,%d) out of canvas axis %d (size %d)",
-                  lo[k], hi[k], k, dims[k]);
-  return FFN_OK;
-}
-
-int grid_for(long total, int block = 256) {
-  long g = (total + block - 1) / block;
-  return (int)std::max<long>(1, std::min<long>(g, 2048));
 }
 
 }  // namespace
@@ -2273,291 +1665,6 @@ int ffn_forward_resident(ffn_engine* e, int n, int repeats) {
   return FFN_OK;
 }
 
-int ffn_engine_set_option(ffn_engine* e, const char* name, int value) {
-  EngineLock lock_(e);
-  if (!e || !name) return fail(FFN_ERR_ARG, "null argument");
-
-  if (std::strcmp(name, "conv_variant") == 0) {
-    if (value == -1) value = e->exact_variant;  // "the exact-f32 kernel of this FoV"
-    if (value != 0 && value != 2 && !(value >= 6 && value <= 10))
-      return fail(FFN_ERR_ARG, "conv_variant must be 0, 2, 6, 7, 8, 9 or 10 (1, 3, 4, 5 "
-                               "were removed in ABI 7)");
-    if (value == 10 && !e->h_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 10 unsupported for this fov / depth / device "
-                               "(80-voxel workgroups, two per CU, all resident)");
-    if (value >= 6 && e->weights_set && !e->fp16_ok)
-      return fail(FFN_ERR_ARG, "conv_variant %d: a weight is outside the fp16 range",
-                  value);
-    if (value == 6 && !e->d_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 6 unsupported for this fov / depth");
-    if (value == 7 && !e->e_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 7 unsupported for this fov / depth");
-    if (value == 8 && !e->m_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 8 unsupported for this fov / depth");
-    if (value == 9 && !e->t_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 9 unsupported for this fov / depth "
-                               "(257 .. 512 chunks of 128 voxels)");
-    if (value >= 6 && e->weights_set && !e->d_weights_ok)
-      return fail(FFN_ERR_ARG, "conv_variant 6: a weight x 2^11 is outside the fp16 range");
-    if (value == 2 && !(e->Rc == 256 || e->Rc == 288))
-      return fail(FFN_ERR_ARG, "conv_variant %d unsupported for this fov", value);
-    return switch_variant(e, value);
-  }
-  if (std::strcmp(name, "profile_every") == 0) {
-    if (value < 1) return fail(FFN_ERR_ARG, "profile_every must be >= 1");
-    e->prof_every = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "sync_mode") == 0) {
-    if (value != 0 && value != 1) return fail(FFN_ERR_ARG, "sync_mode must be 0 or 1");
-    e->sync_mode = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "debug_clock") == 0) {
-    e->dbg_clock = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "batch_chunks") == 0) {
-    // steps with >= 2 FoVs under conv_variant 6: 0 = the same kernel, 1 = its
-    // 96-voxel form (bit-identical), 2 = conv32m (another summation order)
-    if (value < 0 || value > 2) return fail(FFN_ERR_ARG, "batch_chunks 0..2");
-    e->batch_chunks = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "tail_batched") == 0) {
-    // conv_variant 9: 1 = steps with >= 2 FoVs also split off the tail (in
-    // 96-voxel workgroups): every voxel then gets the same bits whatever the
-    // batch, at 5-10 % of the batched rate
-    e->tail_batched = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "flow_debug") == 0) {
-    e->flow_debug = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "flow_pace") == 0) {
-    if (value < -1 || value > 5000)
-      return fail(FFN_ERR_ARG, "flow_pace: -1 (measured), 0 (off) .. 5000 (10-ns ticks)");
-    e->flow_pace = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "flow_pace_spread") == 0) {
-    if (value < -1 || value > 5000) return fail(FFN_ERR_ARG, "flow_pace_spread: -1 .. 5000");
-    e->flow_pace_spread = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "flow_pace_tail") == 0) {
-    if (value < 0 || value > 5000) return fail(FFN_ERR_ARG, "flow_pace_tail: 0 .. 5000");
-    e->flow_pace_tail = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "flow") == 0) {
-    // single-FoV steps of conv_variant 9: 0 one dependent launch per conv; 1 the
-    // same launches with the flagged hand-off compiled in; 2 the resident stack
-    // (conv32ps: one launch for all convs).  Same bits in every mode.
-    if (value < 0 || value > 2) return fail(FFN_ERR_ARG, "flow: 0, 1 or 2");
-    if (value && !e->t_ok)
-      return fail(FFN_ERR_ARG, "flow needs conv32mt's geometry (conv_variant 9)");
-    if (value && e->depth < 2) return fail(FFN_ERR_ARG, "flow needs depth >= 2");
-    if (value == 2 && !e->flow_fits)
-      return fail(FFN_ERR_ARG, "flow 2: this device cannot hold the resident launch's "
-                  "workgroups all at once (compute units x occupancy)");
-    drop_spec(e);
-    e->flow = value;
-    e->flow_auto_off = 0;
-    e->flow_strikes = 0;
-    e->flow_skip = 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "spec_force_mismatch") == 0) {
-    e->spec_force_mismatch = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "fuse_paste") == 0) {
-    e->fuse_paste = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "fuse_conv0a") == 0) {
-    drop_spec(e);
-    e->fuse_conv0a = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "paste_blocks") == 0) {
-    if (value < 0 || value > 1024) return fail(FFN_ERR_ARG, "paste_blocks out of range");
-    e->paste_blocks = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "debug_fused_twice") == 0) {
-    e->debug_fused_twice = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "debug_submit_delay_ns") == 0) {
-    e->debug_submit_delay_ns = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "stack_ahead") == 0) {
-    // the next step's resident stack behind its speculative conv0_a, ahead of the host
-    drop_spec(e);
-    e->stack_ahead = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "speculate") == 0) {
-    // single-FoV steps of ffn_canvas_segment_at: queue the next step's conv0_a
-    // behind the paste, ahead of the host's turn-around (SpecArgs)
-    drop_spec(e);
-    e->speculate = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "stat_reset") == 0) {
-    e->stat_spec_launched = e->stat_spec_hits = e->stat_spec_mismatch = 0;
-    e->stat_ahead_used = e->stat_ahead_wasted = 0;
-    e->stat_spec_miss_full = e->stat_spec_miss_short = 0;
-    e->stat_segturn_queue_ns = e->stat_segturn_wait_ns = 0;
-    e->stat_segturn_calls = 0;
-    e->stat_calls = e->stat_items = 0;
-    std::memset(e->stat_hist, 0, sizeof(e->stat_hist));
-    e->stat_turn_host_ns = e->stat_launch_host_ns = 0;
-    e->stat_turn_host_count = 0;
-    e->t_arrived_ns = 0;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemset(e->d_stamps, 0, 32 * sizeof(long long)));
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "debug_fused_trace") == 0) {
-    // the N-th single-FoV step from now stamps when its launches' roles ran
-    // (ConvStackTab::stamps [4 .. 11]; read with debug_fused_stamp_K)
-    // (minima at +inf, maxima at 0 -- here, not in the stream of the traced step)
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemset(e->d_stamps + 4, 0x7f, 4 * sizeof(long long)));
-    HIP_TRY(hipMemset(e->d_stamps + 8, 0, 4 * sizeof(long long)));
-    HIP_TRY(hipMemset(e->d_stamps + 12, 0, 20 * sizeof(long long)));
-    HIP_TRY(hipMemset(e->d_stamps + 32, 0, 1024 * sizeof(long long)));
-    e->fused_trace_in = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "debug_layer") == 0) {
-    e->dbg_layer = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "ablate") == 0) {
-    e->ablate = value;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "fuse_head") == 0) {
-    e->fuse_head = value != 0;
-    return FFN_OK;
-  }
-  if (std::strcmp(name, "store_policy") == 0) {
-    if (value < 0 || value > 2) return fail(FFN_ERR_ARG, "store_policy 0..2");
-    e->store_policy = value;
-    return FFN_OK;
-  }
-  return fail(FFN_ERR_ARG, "unknown option '%s'", name);
-}
-
-int ffn_engine_get_option(ffn_engine* e, const char* name, int* value) {
-  EngineLock lock_(e);
-  if (!e || !name || !value) return fail(FFN_ERR_ARG, "null argument");
-  if (std::strcmp(name, "conv_variant") == 0) *value = e->conv_variant;
-  else if (std::strcmp(name, "fuse_head") == 0) *value = e->fuse_head;
-  else if (std::strcmp(name, "exact_variant") == 0) *value = e->exact_variant;
-  else if (std::strcmp(name, "stat_step_calls") == 0) *value = (int)e->stat_calls;
-  else if (std::strcmp(name, "stat_step_items") == 0) *value = (int)e->stat_items;
-  else if (std::strcmp(name, "speculate") == 0) *value = e->speculate;
-  else if (std::strcmp(name, "stack_ahead") == 0) *value = e->stack_ahead;
-  else if (std::strcmp(name, "paste_blocks") == 0) *value = e->paste_blocks;
-  else if (std::strcmp(name, "stat_segturn_queue_ns") == 0)
-    *value = e->stat_segturn_calls ? (int)(e->stat_segturn_queue_ns / e->stat_segturn_calls) : 0;
-  else if (std::strcmp(name, "stat_segturn_wait_ns") == 0)
-    *value = e->stat_segturn_calls ? (int)(e->stat_segturn_wait_ns / e->stat_segturn_calls) : 0;
-  else if (std::strcmp(name, "stat_segturn_calls") == 0) *value = (int)e->stat_segturn_calls;
-  else if (std::strcmp(name, "stat_spec_miss_full") == 0) *value = (int)e->stat_spec_miss_full;
-  else if (std::strcmp(name, "stat_spec_miss_short") == 0) *value = (int)e->stat_spec_miss_short;
-  else if (std::strcmp(name, "stat_ahead_used") == 0) *value = (int)e->stat_ahead_used;
-  else if (std::strcmp(name, "stat_ahead_wasted") == 0) *value = (int)e->stat_ahead_wasted;
-  else if (std::strcmp(name, "fuse_paste") == 0) *value = e->fuse_paste;
-  else if (std::strcmp(name, "fuse_conv0a") == 0) *value = e->fuse_conv0a;
-  else if (std::strcmp(name, "stat_spec_launched") == 0)
-    *value = (int)e->stat_spec_launched;
-  else if (std::strcmp(name, "stat_spec_hits") == 0) *value = (int)e->stat_spec_hits;
-  else if (std::strcmp(name, "stat_spec_mismatch") == 0)
-    *value = (int)e->stat_spec_mismatch;
-  else if (std::strcmp(name, "stat_many_carried") == 0)
-    *value = (int)e->stat_many_carried;
-  else if (std::strcmp(name, "flow") == 0) *value = e->flow;
-  else if (std::strcmp(name, "flow_auto_off") == 0) *value = e->flow_auto_off;
-  else if (std::strcmp(name, "stat_flow_voids") == 0) *value = (int)e->stat_flow_voids;
-  else if (std::strcmp(name, "stat_turn_host_ns") == 0)
-    *value = e->stat_turn_host_count
-                 ? (int)(e->stat_turn_host_ns / e->stat_turn_host_count) : 0;
-  else if (std::strcmp(name, "stat_launch_host_ns") == 0)
-    *value = e->stat_turn_host_count
-                 ? (int)(e->stat_launch_host_ns / e->stat_turn_host_count) : 0;
-  else if (std::strcmp(name, "stat_turn_count") == 0) *value = (int)e->stat_turn_host_count;
-  else if (std::strcmp(name, "stat_ahead_aborted") == 0) {
-    long long st[4] = {0, 0, 0, 0};
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(st, e->d_stamps, sizeof(st), hipMemcpyDeviceToHost));
-    *value = (int)st[3];
-  }
-  else if (std::strcmp(name, "stat_turn_gpu_ns") == 0) {
-    long long st[4] = {0, 0, 0, 0};
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(st, e->d_stamps, sizeof(st), hipMemcpyDeviceToHost));
-    *value = st[2] ? (int)(st[1] * 10 / st[2]) : 0;
-  }
-  else if (std::strncmp(name, "debug_fused_stamp_", 18) == 0) {
-    // stamp k (4 .. 11) minus the stack's first entry [7], in 10-ns ticks
-    const int k = std::atoi(name + 18);
-    long long st[32 + 1024];
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(st, e->d_stamps, sizeof(st), hipMemcpyDeviceToHost));
-    for (int w = 0; w < 512; ++w) st[25] = std::max(st[25], st[32 + w]);  // (per-workgroup ends)
-    {  // [27]: main workgroups that share their CU with another main workgroup
-      std::map<unsigned, int> per_cu;
-      for (int w = 0; w < 512; ++w) {
-        const unsigned v = (unsigned)st[32 + 512 + w];
-        if (st[32 + 512 + w] != 0 && ((v - 1) >> 31)) per_cu[(v - 1) & 0x7fffffffu] += 1;
-      }
-      long long shared = 0;
-      for (const auto& kv : per_cu) if (kv.second > 1) shared += kv.second;
-      st[27] = st[4] + shared;  // (the getter subtracts the origin)
-      if (!e->stack_ahead) st[27] = st[7] + shared;
-    }
-    if (k < 4 || k > 27 || k == 15) return fail(FFN_ERR_ARG, "debug_fused_stamp_4 .. 27");
-    // (stack_ahead: the stack inside the traced window is the NEXT step's; the fused
-    // launch's first faces entry [4] is the origin then)
-    *value = (int)(st[k] - (e->stack_ahead ? st[4] : st[7]));
-  }
-  else if (std::strcmp(name, "flow_pace") == 0) *value = e->flow_pace;
-  else if (std::strcmp(name, "flow_pace_now") == 0)
-    *value = e->flow_pace < 0 ? e->pace_auto : e->flow_pace;
-  else if (std::strcmp(name, "flow_pace_free_ns") == 0) *value = (int)(e->pace_auto_us[0] * 1e3f);
-  else if (std::strcmp(name, "flow_pace_best_ns") == 0) *value = (int)(e->pace_auto_us[1] * 1e3f);
-  else if (std::strcmp(name, "stat_flow_timeouts") == 0) {
-    unsigned v = 0;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(&v, e->flow_err, sizeof(v), hipMemcpyDeviceToHost));
-    *value = (int)v;
-  }
-  else if (std::strncmp(name, "stat_hist_", 10) == 0) {
-    const int k = std::atoi(name + 10);
-    if (k < 0 || k > 64) return fail(FFN_ERR_ARG, "stat_hist_<0..64>");
-    *value = (int)e->stat_hist[k];
-  }
-  else if (std::strcmp(name, "store_policy") == 0) *value = e->store_policy;
-  else if (std::strcmp(name, "sync_mode") == 0) *value = e->sync_mode;
-  else if (std::strcmp(name, "profile_every") == 0) *value = e->prof_every;
-  else return fail(FFN_ERR_ARG, "unknown option '%s'", name);
-  return FFN_OK;
-}
-
 int ffn_engine_set_pred_size(ffn_engine* e, const int32_t pred_zyx[3]) {
   EngineLock lock_(e);
   if (!e || !pred_zyx) return fail(FFN_ERR_ARG, "null argument");
@@ -2589,245 +1696,6 @@ int ffn_engine_set_pred_size(ffn_engine* e, const int32_t pred_zyx[3]) {
     g.Vp *= pred_zyx[a];
     g.crop |= pred_zyx[a] != f[a];
   }
-  return FFN_OK;
-}
-
-int ffn_engine_debug_flow_trace(ffn_engine* e, long long* out, int max_slots) {
-  EngineLock lock_(e);
-  if (!e || !out) return fail(FFN_ERR_ARG, "null argument");
-  if (!e->flow_trace) return fail(FFN_ERR_ARG, "no flow trace on this engine (conv_variant 9)");
-  if (max_slots < 0 || max_slots > e->flow_trace_slots)
-    return fail(FFN_ERR_ARG, "max_slots must be 0..%d", e->flow_trace_slots);
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  const size_t row = (size_t)kFlowTraceLayers * 8 * sizeof(long long);
-  HIP_TRY(hipMemcpy(out, e->flow_trace, row * max_slots, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemset(e->flow_trace, 0, row * e->flow_trace_slots));
-  return FFN_OK;
-}
-
-int ffn_engine_debug_workgroups(ffn_engine* e, long long* out, int max_wgs) {
-  EngineLock lock_(e);
-  if (!e || !out) return fail(FFN_ERR_ARG, "null argument");
-  if (max_wgs < 0 || max_wgs > kDbgMaxWgs)
-    return fail(FFN_ERR_ARG, "max_wgs must be 0..%d", kDbgMaxWgs);
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(out, e->d_dbg + 24, (size_t)4 * max_wgs * sizeof(long long),
-                    hipMemcpyDeviceToHost));
-  // the next run starts from zeros (a workgroup that did not run leaves them)
-  HIP_TRY(hipMemset(e->d_dbg + 24, 0, (size_t)4 * kDbgMaxWgs * sizeof(long long)));
-  return FFN_OK;
-}
-
-int ffn_engine_debug_clocks(ffn_engine* e, long long* out24) {
-  EngineLock lock_(e);
-  if (!e || !out24) return fail(FFN_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(out24, e->d_dbg, 24 * sizeof(long long), hipMemcpyDeviceToHost));
-  return FFN_OK;
-}
-
-int ffn_engine_synchronize(ffn_engine* e) {
-  EngineLock lock_(e);
-  if (!e) return fail(FFN_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return FFN_OK;
-}
-
-int ffn_engine_set_profiling(ffn_engine* e, int mode) {
-  EngineLock lock_(e);
-  if (!e) return fail(FFN_ERR_ARG, "null argument");
-  if (mode < 0 || mode > 2) return fail(FFN_ERR_ARG, "mode must be 0, 1 or 2");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = flush_events(e);
-  if (rc) return rc;
-  e->chain_launches_pending.clear();
-  e->prof_mode = mode;
-  return FFN_OK;
-}
-
-int ffn_engine_get_profile(ffn_engine* e, double* conv_ms_total,
-                           int64_t* conv_launches, int reset) {
-  EngineLock lock_(e);
-  if (!e) return fail(FFN_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = flush_events(e);
-  if (rc) return rc;
-  if (conv_ms_total) *conv_ms_total = e->conv_ms;
-  if (conv_launches) *conv_launches = e->conv_launches;
-  if (reset) {
-    e->conv_ms = 0.0;
-    e->conv_launches = 0;
-    e->prof_samples.clear();
-  }
-  return FFN_OK;
-}
-
-int ffn_engine_get_profile_samples(ffn_engine* e, float* out_ms, int max_n, int* n) {
-  EngineLock lock_(e);
-  if (!e || !n || (max_n > 0 && !out_ms)) return fail(FFN_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = flush_events(e);
-  if (rc) return rc;
-  const int k = (int)std::min<size_t>(e->prof_samples.size(), (size_t)std::max(max_n, 0));
-  for (int i = 0; i < k; ++i) out_ms[i] = e->prof_samples[i];
-  *n = (int)e->prof_samples.size();
-  return FFN_OK;
-}
-
-/* ------------------------------- canvas ---------------------------------- */
-
-namespace {
-
-// image_f32 (already normalised) or image_u8 + the normalisation constants
-int canvas_create(ffn_engine* e, const float* image_f32, const uint8_t* image_u8,
-                  float mean, float stddev, const int32_t shape_zyx[3],
-                  ffn_canvas** out) {
-  EngineLock lock_(e);
-  if (!e || (!image_f32 && !image_u8) || !shape_zyx || !out)
-    return fail(FFN_ERR_ARG, "null argument");
-  *out = nullptr;
-  for (int k = 0; k < 3; ++k)
-    if (shape_zyx[k] < 1) return fail(FFN_ERR_ARG, "bad canvas shape");
-  if (image_u8 && !(stddev != 0.0f))
-    return fail(FFN_ERR_ARG, "image_stddev must be non-zero");
-  HIP_TRY(hipSetDevice(e->device));
-  ffn_canvas* c = new ffn_canvas();
-  c->engine = e;
-  c->cz = shape_zyx[0];
-  c->cy = shape_zyx[1];
-  c->cx = shape_zyx[2];
-  c->nvox = (size_t)c->cz * c->cy * c->cx;
-  hipError_t err = hipSuccess;
-  if (image_f32) {
-    err = hipMalloc(&c->image, c->nvox * sizeof(float));
-    if (err == hipSuccess)
-      err = hipMemcpy(c->image, image_f32, c->nvox * sizeof(float),
-                      hipMemcpyHostToDevice);
-  } else {
-    // (image.astype(np.float32) - image_mean) / image_stddev (runner.py:383-385):
-    // two correctly rounded f32 operations per value, evaluated here for the
-    // 256 possible inputs -- the device only looks the result up, so a uint8
-    // canvas is bit-identical to the f32 one by construction
-    float lut[256];
-    for (int v = 0; v < 256; ++v) {
-      volatile float d = (float)v - mean;  // volatile: no fused / widened form
-      lut[v] = d / stddev;
-    }
-    err = hipMalloc(&c->image_u8, c->nvox);
-    if (err == hipSuccess) err = hipMalloc(&c->image_lut, sizeof(lut));
-    if (err == hipSuccess)
-      err = hipMemcpy(c->image_u8, image_u8, c->nvox, hipMemcpyHostToDevice);
-    if (err == hipSuccess)
-      err = hipMemcpy(c->image_lut, lut, sizeof(lut), hipMemcpyHostToDevice);
-  }
-  if (err == hipSuccess) err = hipMalloc(&c->seed, c->nvox * sizeof(float));
-  if (err == hipSuccess) err = hipMalloc(&c->seg, c->nvox * sizeof(int32_t));
-  if (err == hipSuccess) err = hipMemset(c->seg, 0, c->nvox * sizeof(int32_t));
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(fill_u32_kernel, dim3(2048), dim3(256), 0, e->stream,
-                       reinterpret_cast<uint32_t*>(c->seed), 0x7fc00000u, c->nvox);
-    err = hipStreamSynchronize(e->stream);
-  }
-  if (err != hipSuccess) {
-    int rc = fail(FFN_ERR_HIP, "canvas allocation failed: %s", hipGetErrorString(err));
-    ffn_canvas_destroy(c);
-    return rc;
-  }
-  {
-    const hipError_t ee = hipEventCreateWithFlags(&c->ev_util, hipEventDisableTiming);
-    if (ee != hipSuccess) {
-      int rc = fail(FFN_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(ee));
-      ffn_canvas_destroy(c);
-      return rc;
-    }
-  }
-  e->canvases.push_back(c);
-  *out = c;
-  return FFN_OK;
-}
-
-}  // namespace
-
-int ffn_canvas_create(ffn_engine* e, const float* image_f32,
-                      const int32_t shape_zyx[3], ffn_canvas** out) {
-  if (!image_f32) return fail(FFN_ERR_ARG, "null argument");
-  return canvas_create(e, image_f32, nullptr, 0.f, 1.f, shape_zyx, out);
-}
-
-int ffn_canvas_create_u8(ffn_engine* e, const uint8_t* image_u8,
-                         const int32_t shape_zyx[3], float image_mean,
-                         float image_stddev, ffn_canvas** out) {
-  if (!image_u8) return fail(FFN_ERR_ARG, "null argument");
-  return canvas_create(e, nullptr, image_u8, image_mean, image_stddev, shape_zyx,
-                       out);
-}
-
-namespace {
-int resolve_many_carry(ffn_engine* e, const ffn_canvas* only = nullptr);
-}
-
-void ffn_canvas_destroy(ffn_canvas* c) {
-  if (c && c->engine) (void)resolve_many_carry(c->engine, c);  // a step in flight
-  EngineLock lock_(c ? c->engine : nullptr);
-  if (!c) return;
-  if (c->engine) {
-    ffn_engine* e = c->engine;
-    drop_spec(e);
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-    (void)hipStreamSynchronize(e->ustream);
-    if (c->ev_util) (void)hipEventDestroy(c->ev_util);
-    e->canvases.erase(std::remove(e->canvases.begin(), e->canvases.end(), c),
-                      e->canvases.end());
-    (void)hipFree(c->image);
-    (void)hipFree(c->image_u8);
-    (void)hipFree(c->image_lut);
-    (void)hipFree(c->seed);
-    (void)hipFree(c->seg);
-    (void)hipFree(c->restrict_planes);
-  }
-  delete c;
-}
-
-int ffn_canvas_init_seed(ffn_canvas* c, const int32_t pos[3], float value) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !pos) return fail(FFN_ERR_ARG, "null argument");
-  if (pos[0] < 0 || pos[0] >= c->cz || pos[1] < 0 || pos[1] >= c->cy ||
-      pos[2] < 0 || pos[2] >= c->cx)
-    return fail(FFN_ERR_ARG, "seed position outside the canvas");
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  if (c->dirty_lo[0] < c->dirty_hi[0]) {
-    long total = 0;
-    Box b = make_box(c, c->dirty_lo, c->dirty_hi, &total);
-    if ((size_t)total * 2 >= c->nvox) {  // most of the volume: linear fill
-      hipLaunchKernelGGL(fill_u32_kernel, dim3(2048), dim3(256), 0, e->ustream,
-                         reinterpret_cast<uint32_t*>(c->seed), 0x7fc00000u,
-                         c->nvox);
-    } else if (total > 0) {
-      hipLaunchKernelGGL((box_fill_kernel<uint32_t>), dim3(grid_for(total)),
-                         dim3(256), 0, e->ustream,
-                         reinterpret_cast<uint32_t*>(c->seed), b, total,
-                         0x7fc00000u);
-    }
-  }
-  {
-    const int lo[3] = {pos[0], pos[1], pos[2]};
-    const int hi[3] = {pos[0] + 1, pos[1] + 1, pos[2] + 1};
-    c->dirty_lo[0] = c->dirty_hi[0] = 0;  // clean, then the seed point itself
-    c->mark_dirty(lo, hi);
-  }
-  const size_t ci = ((size_t)pos[0] * c->cy + pos[1]) * c->cx + pos[2];
-  hipLaunchKernelGGL(set_seed_point_kernel, dim3(1), dim3(1), 0, e->ustream,
-                     c->seed, ci, value);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(lock_.end(e, c));
   return FFN_OK;
 }
 
@@ -3267,6 +2135,11 @@ int resolve_many_carry_locked(ffn_engine* e) {
   e->many_canvases.clear();
   return rc;
 }
+}  // namespace
+
+}  // extern "C"
+
+// (declared in ffn_engine.h: the canvas calls of ffn_canvas.hip resolve it too)
 int resolve_many_carry(ffn_engine* e, const ffn_canvas* only) {
   std::lock_guard<std::mutex> guard(e->many_mu);
   if (only && std::find(e->many_canvases.begin(), e->many_canvases.end(), only) ==
@@ -3274,7 +2147,8 @@ int resolve_many_carry(ffn_engine* e, const ffn_canvas* only) {
     return FFN_OK;
   return resolve_many_carry_locked(e);
 }
-}  // namespace
+
+extern "C" {
 
 int ffn_canvas_segment_at(ffn_canvas* c, const int32_t start[3],
                           const ffn_segment_params* p, int resume,
@@ -3372,562 +2246,6 @@ int ffn_canvas_segment_many_carry(ffn_engine* e, int n, ffn_canvas* const* canva
   return ffn_host::segment_many(n, devs.data(), states.data(), starts, params, resume,
                                 results, finished, batch_step, &e->many_carry, submit,
                                 wait);
-}
-
-int ffn_canvas_segment_history(ffn_canvas* c, size_t first, size_t n,
-                               int32_t* pos, uint32_t* deleted, size_t* total) {
-  if (!c) return fail(FFN_ERR_ARG, "null canvas");
-  if (c->engine)
-    if (int rc = resolve_many_carry(c->engine, c)) return rc;
-  const size_t have = c->loop.history_deleted.size();
-  if (total) *total = have;
-  if (n == 0) return FFN_OK;
-  if (first > have || n > have - first)
-    return fail(FFN_ERR_ARG, "history range [%zu, +%zu) of %zu", first, n, have);
-  if (pos) std::memcpy(pos, c->loop.history.data() + 3 * first, 12 * n);
-  if (deleted) std::memcpy(deleted, c->loop.history_deleted.data() + first, 4 * n);
-  return FFN_OK;
-}
-
-int ffn_canvas_set_restrictor(ffn_canvas* c, const uint8_t* mask,
-                              const uint8_t* seed_mask, const uint8_t* shift_mask,
-                              const int32_t shift_shape[3], const int32_t pre[3],
-                              const int32_t post[3], int32_t scale) {
-  if (!c) return fail(FFN_ERR_ARG, "null canvas");
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  if (shift_mask) {
-    if (!shift_shape || !pre || !post)
-      return fail(FFN_ERR_ARG, "shift mask without its shape / FoV offsets");
-    for (int k = 0; k < 3; ++k) {
-      if (shift_shape[k] < 1) return fail(FFN_ERR_ARG, "bad shift mask shape");
-      // (post >= -1: every numpy stop of is_valid_pos is >= 0 at a position >= 0)
-      if (post[k] < -1) return fail(FFN_ERR_ARG, "shift mask FoV ends before 0");
-    }
-    if (scale < 1) return fail(FFN_ERR_ARG, "shift mask scale must be >= 1");
-  }
-  if (int rc = resolve_many_carry(e, c)) return rc;
-  UtilLock lock_(e);
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  // the old planes: no turn queued on the utility stream may still read them
-  HIP_TRY(hipStreamSynchronize(e->ustream));
-  (void)hipFree(c->restrict_planes);
-  c->restrict_planes = nullptr;
-  c->restrict_plane_words = 0;
-  c->restrict_row_words = 0;
-  std::vector<uint64_t>().swap(c->restrict_host);
-  c->loop.restrict_bits = nullptr;
-  if (!mask && !seed_mask && !shift_mask) return FFN_OK;  // cleared
-
-  const int Z = c->cz, Y = c->cy, X = c->cx;
-  const int W = (X + 63) / 64;
-  const size_t pw = (size_t)Z * Y * W;
-  const size_t wave_blocks = std::min<size_t>((pw + 3) / 4, 8192);  // 4 waves / block
-  unsigned long long* planes = nullptr;
-  uint8_t* d_src = nullptr;
-  unsigned long long *d_ax = nullptr, *d_ay = nullptr;
-  hipError_t err = hipMalloc(&planes, 2 * pw * sizeof(uint64_t));
-  // mask -> pos plane, seed mask -> seed plane: one u8 temporary at a time
-  const uint8_t* srcs[2] = {mask, seed_mask};
-  for (int k = 0; k < 2 && err == hipSuccess; ++k) {
-    unsigned long long* plane = planes + k * pw;
-    if (!srcs[k]) {
-      err = hipMemsetAsync(plane, 0, pw * sizeof(uint64_t), e->ustream);
-      continue;
-    }
-    err = hipMalloc(&d_src, c->nvox);
-    if (err == hipSuccess) err = hipMemcpy(d_src, srcs[k], c->nvox, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-      hipLaunchKernelGGL(restrict_pack_kernel, dim3((unsigned)wave_blocks), dim3(256), 0,
-                         e->ustream, d_src, (long)Z * Y, X, W, plane);
-      err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
-    (void)hipFree(d_src);
-    d_src = nullptr;
-  }
-  if (shift_mask && err == hipSuccess) {
-    const int Zs = shift_shape[0], Ys = shift_shape[1], Xs = shift_shape[2];
-    const size_t ns = (size_t)Zs * Ys * Xs;
-    const size_t nax = (size_t)Zs * Ys * W, nay = (size_t)Zs * Y * W;
-    err = hipMalloc(&d_src, ns);
-    if (err == hipSuccess) err = hipMalloc(&d_ax, nax * sizeof(uint64_t));
-    if (err == hipSuccess) err = hipMalloc(&d_ay, nay * sizeof(uint64_t));
-    if (err == hipSuccess) err = hipMemcpy(d_src, shift_mask, ns, hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-      hipLaunchKernelGGL(restrict_shift_x_kernel,
-                         dim3((unsigned)std::min<size_t>((nax + 3) / 4, 8192)), dim3(256),
-                         0, e->ustream, d_src, (long)Zs * Ys, Xs, X, W, pre[2], post[2],
-                         scale, d_ax);
-      hipLaunchKernelGGL(restrict_shift_y_kernel, dim3(grid_for((long)nay)), dim3(256), 0,
-                         e->ustream, d_ax, Zs, Ys, Y, W, pre[1], post[1], scale, d_ay);
-      hipLaunchKernelGGL(restrict_shift_z_kernel, dim3(grid_for((long)pw)), dim3(256), 0,
-                         e->ustream, d_ay, Zs, Z, Y, W, pre[0], post[0], planes);
-      err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
-    (void)hipFree(d_src);
-    (void)hipFree(d_ax);
-    (void)hipFree(d_ay);
-    d_src = nullptr;
-  }
-  if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
-  // the host loop's copy of the pos plane (1 bit / voxel)
-  if (err == hipSuccess) {
-    try {
-      c->restrict_host.resize(pw);
-    } catch (const std::bad_alloc&) {
-      (void)hipFree(planes);
-      return fail(FFN_ERR_ARG, "no host memory for the restriction plane");
-    }
-    err = hipMemcpy(c->restrict_host.data(), planes, pw * sizeof(uint64_t),
-                    hipMemcpyDeviceToHost);
-  }
-  if (err != hipSuccess) {
-    (void)hipFree(planes);
-    std::vector<uint64_t>().swap(c->restrict_host);
-    return fail(FFN_ERR_HIP, "restriction planes: %s", hipGetErrorString(err));
-  }
-  c->restrict_planes = planes;
-  c->restrict_plane_words = pw;
-  c->restrict_row_words = W;
-  c->loop.restrict_bits = c->restrict_host.data();
-  c->loop.restrict_dims[0] = Z;
-  c->loop.restrict_dims[1] = Y;
-  c->loop.restrict_dims[2] = X;
-  c->loop.restrict_row_words = W;
-  return FFN_OK;
-}
-
-int ffn_canvas_read_restriction(ffn_canvas* c, const int32_t lo[3],
-                                const int32_t hi[3], uint8_t* dst) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (int rc = check_canvas(c)) return rc;
-  if (!lo || !hi || !dst) return fail(FFN_ERR_ARG, "null argument");
-  if (int rc = check_box(c, lo, hi)) return rc;
-  long total = 0;
-  const Box b = make_box(c, lo, hi, &total);
-  if (total <= 0) return FFN_OK;
-  if (!c->restrict_planes) {  // no restrictor: nothing is blocked
-    std::memset(dst, 0, (size_t)total);
-    return FFN_OK;
-  }
-  ffn_engine* e = c->engine;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c, true));
-  uint8_t* d_out = nullptr;
-  HIP_TRY(hipMalloc(&d_out, (size_t)total));
-  hipLaunchKernelGGL(restrict_read_kernel, dim3(grid_for(total)), dim3(256), 0,
-                     e->ustream, c->restrict_planes, c->restrict_plane_words, c->cy,
-                     c->restrict_row_words, b.lo[0], b.lo[1], b.lo[2], b.n[1], b.n[2],
-                     total, d_out);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipStreamSynchronize(e->ustream);
-  if (err == hipSuccess) err = hipMemcpy(dst, d_out, (size_t)total, hipMemcpyDeviceToHost);
-  (void)hipFree(d_out);
-  if (err != hipSuccess)
-    return fail(FFN_ERR_HIP, "read_restriction: %s", hipGetErrorString(err));
-  return FFN_OK;
-}
-
-int ffn_canvas_take_restricted_skips(ffn_canvas* c, int64_t* out) {
-  if (!c || !out) return fail(FFN_ERR_ARG, "null argument");
-  if (c->engine)
-    if (int rc = resolve_many_carry(c->engine, c)) return rc;
-  *out = c->loop.skip_restricted;
-  c->loop.skip_restricted = 0;
-  return FFN_OK;
-}
-
-int ffn_canvas_read_points(ffn_canvas* c, int n, const int32_t* pos,
-                           float* seed_out, int32_t* seg_out) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !pos || !seed_out || !seg_out) return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1) return FFN_OK;
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c, true));
-  const size_t pb = sizeof(int32_t) * 3 * n;
-  const size_t pbr = (pb + 15) & ~(size_t)15;
-  int rc = ensure_scratch(e, pbr + 8 * (size_t)n);
-  if (rc) return rc;
-  char* hs = static_cast<char*>(e->h_scratch);
-  char* ds = static_cast<char*>(e->d_scratch);
-  std::memcpy(hs, pos, pb);
-  HIP_TRY(hipMemcpyAsync(ds, hs, pb, hipMemcpyHostToDevice, e->ustream));
-  float* d_seed = reinterpret_cast<float*>(ds + pbr);
-  int32_t* d_seg = reinterpret_cast<int32_t*>(ds + pbr + 4 * (size_t)n);
-  hipLaunchKernelGGL(points_read_kernel, dim3((n + 63) / 64), dim3(64), 0,
-                     e->ustream, c->seed, c->seg, c->cz, c->cy, c->cx, n,
-                     reinterpret_cast<const int32_t*>(ds), d_seed, d_seg);
-  HIP_TRY(hipMemcpyAsync(hs + pbr, ds + pbr, 8 * (size_t)n, hipMemcpyDeviceToHost,
-                         e->ustream));
-  HIP_TRY(lock_.wait(e, c));
-  std::memcpy(seed_out, hs + pbr, 4 * (size_t)n);
-  std::memcpy(seg_out, hs + pbr + 4 * (size_t)n, 4 * (size_t)n);
-  return FFN_OK;
-}
-
-int ffn_canvas_write_seg_points(ffn_canvas* c, int n, const int32_t* pos,
-                                const int32_t* values) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !pos || !values) return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1) return FFN_OK;
-  for (int k = 0; k < n; ++k)
-    if (pos[3 * k] < 0 || pos[3 * k] >= c->cz || pos[3 * k + 1] < 0 ||
-        pos[3 * k + 1] >= c->cy || pos[3 * k + 2] < 0 || pos[3 * k + 2] >= c->cx)
-      return fail(FFN_ERR_ARG, "point %d outside the canvas", k);
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  if (n == 1) {  // (the -1 marker of a rejected seed: nothing to wait for)
-    const size_t ci = ((size_t)pos[0] * c->cy + pos[1]) * c->cx + pos[2];
-    hipLaunchKernelGGL(set_seg_point_kernel, dim3(1), dim3(1), 0, e->ustream, c->seg,
-                       ci, values[0]);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(lock_.end(e, c));
-    return FFN_OK;
-  }
-  const size_t pb = sizeof(int32_t) * 3 * n;
-  const size_t pbr = (pb + 15) & ~(size_t)15;
-  int rc = ensure_scratch(e, pbr + 4 * (size_t)n);
-  if (rc) return rc;
-  char* hs = static_cast<char*>(e->h_scratch);
-  char* ds = static_cast<char*>(e->d_scratch);
-  std::memcpy(hs, pos, pb);
-  std::memcpy(hs + pbr, values, 4 * (size_t)n);
-  HIP_TRY(hipMemcpyAsync(ds, hs, pbr + 4 * (size_t)n, hipMemcpyHostToDevice,
-                         e->ustream));
-  hipLaunchKernelGGL(points_write_seg_kernel, dim3((n + 63) / 64), dim3(64), 0,
-                     e->ustream, c->seg, c->cy, c->cx, n,
-                     reinterpret_cast<const int32_t*>(ds),
-                     reinterpret_cast<const int32_t*>(ds + pbr));
-  HIP_TRY(lock_.wait(e, c));
-  return FFN_OK;
-}
-
-int ffn_canvas_any_segmented(ffn_canvas* c, const int32_t lo[3],
-                             const int32_t hi[3], int32_t* out) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !lo || !hi || !out) return fail(FFN_ERR_ARG, "null argument");
-  // numpy slicing clips to the array bounds (inference.py:575-578)
-  int32_t l[3], h[3];
-  const int dims[3] = {c->cz, c->cy, c->cx};
-  for (int k = 0; k < 3; ++k) {
-    l[k] = std::max(lo[k], 0);
-    h[k] = std::min(hi[k], dims[k]);
-    if (h[k] <= l[k]) {
-      *out = 0;
-      return FFN_OK;
-    }
-  }
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  int rc = ensure_scratch(e, 16);
-  if (rc) return rc;
-  long total;
-  Box b = make_box(c, l, h, &total);
-  HIP_TRY(hipMemsetAsync(e->d_scratch, 0, 4, e->ustream));
-  hipLaunchKernelGGL(any_segmented_kernel, dim3(grid_for(total)), dim3(256), 0,
-                     e->ustream, c->seg, b, total,
-                     static_cast<int32_t*>(e->d_scratch));
-  HIP_TRY(hipMemcpyAsync(e->h_scratch, e->d_scratch, 4, hipMemcpyDeviceToHost,
-                         e->ustream));
-  HIP_TRY(lock_.wait(e, c));
-  *out = *static_cast<int32_t*>(e->h_scratch);
-  return FFN_OK;
-}
-
-int ffn_canvas_commit_count(ffn_canvas* c, const int32_t lo[3],
-                            const int32_t hi[3], float segment_threshold,
-                            int32_t max_existing_id, ffn_commit_counts* counts,
-                            int32_t max_overlaps, int32_t* overlap_ids,
-                            int64_t* overlap_counts) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !lo || !hi || !counts) return fail(FFN_ERR_ARG, "null argument");
-  int rc = check_box(c, lo, hi);
-  if (rc) return rc;
-  if (max_existing_id < 0) max_existing_id = 0;
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  // the turn's count and publish kernels: two launches, the answer polled
-  const int novl = overlap_ids && overlap_counts
-                       ? std::max(std::min(max_overlaps, max_existing_id), 0) : 0;
-  rc = ensure_turn(e, 0, (size_t)max_existing_id + 1, (size_t)novl);
-  if (rc) return rc;
-  const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
-  char* ds = static_cast<char*>(e->d_turn);
-  auto* d_part = reinterpret_cast<unsigned long long*>(ds + lay.o_part);
-  auto* d_hist = reinterpret_cast<unsigned*>(ds + lay.o_hist);
-  if (++e->turn_seq == 0) ++e->turn_seq;
-  long total;
-  Box b = make_box(c, lo, hi, &total);
-  const long rows = total > 0 ? (long)b.n[0] * b.n[1] : 0;
-  const int xs = row_lanes_log2(b.n[2]);
-  const int nparts = rows > 0 ? turn_grid(rows, xs) : 0;
-  if (nparts > 0)
-    hipLaunchKernelGGL(turn_count_kernel, dim3(nparts), dim3(256), 0, e->ustream, c->seed,
-                       c->seg, b, rows, xs, segment_threshold, max_existing_id,
-                       max_existing_id < kTurnHistLds ? 1 : 0, d_part, d_hist);
-  hipLaunchKernelGGL(turn_publish_kernel, dim3(1), dim3(1024), 0, e->ustream,
-                     reinterpret_cast<const TurnRecord*>(ds), d_part, nparts, d_hist,
-                     max_existing_id, novl, nullptr, nullptr, nullptr, 0, 0, 0,
-                     e->h_turn_dev + lay.w_pub, e->turn_seq);
-  HIP_TRY(hipGetLastError());
-  const TurnPub pub{e->h_turn + lay.w_pub, e->turn_seq, 0};
-  HIP_TRY(lock_.wait_published(e, c, [&] { return pub.arrived(); }));
-  e->turn_hist_clean = true;
-  counts->raw_segmented_voxels = (int64_t)(pub.at(0) | (uint64_t)pub.at(1) << 32);
-  counts->actual_segmented_voxels = (int64_t)(pub.at(2) | (uint64_t)pub.at(3) << 32);
-  counts->num_overlapped_ids = pub.overlaps(overlap_ids, overlap_counts);
-  return FFN_OK;
-}
-
-int ffn_canvas_commit_assign(ffn_canvas* c, const int32_t lo[3],
-                             const int32_t hi[3], float segment_threshold,
-                             int32_t segment_id) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !lo || !hi) return fail(FFN_ERR_ARG, "null argument");
-  int rc = check_box(c, lo, hi);
-  if (rc) return rc;
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(lock_.begin(e, c));
-  long total;
-  Box b = make_box(c, lo, hi, &total);
-  if (total > 0)
-    hipLaunchKernelGGL(commit_assign_kernel, dim3(grid_for(total)), dim3(256), 0,
-                       e->ustream, c->seed, c->seg, b, total, segment_threshold,
-                       segment_id);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(lock_.end(e, c));
-  return FFN_OK;
-}
-
-int ffn_canvas_segment_turn(ffn_canvas* c, const ffn_turn_request* rq,
-                            const int32_t* cand, ffn_turn_result* out,
-                            int32_t max_overlaps, int32_t* overlap_ids,
-                            int64_t* overlap_counts, int32_t* cand_flags,
-                            float* cand_seed, int32_t* cand_seg) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !rq || !out) return fail(FFN_ERR_ARG, "null argument");
-  const int n = rq->num_candidates;
-  if (n < 0 || (n > 0 && (!cand || !cand_flags || !cand_seed || !cand_seg)))
-    return fail(FFN_ERR_ARG, "candidate arrays");
-  int rc = FFN_OK;
-  if (rq->do_commit && (rc = check_box(c, rq->lo, rq->hi))) return rc;
-  auto inside = [&](const int32_t* p) {
-    return p[0] >= 0 && p[0] < c->cz && p[1] >= 0 && p[1] < c->cy && p[2] >= 0 &&
-           p[2] < c->cx;
-  };
-  if (rq->mark_mode && !inside(rq->mark_pos))
-    return fail(FFN_ERR_ARG, "marker outside the canvas");
-  for (int k = 0; k < n; ++k)
-    if (!inside(cand + 3 * k)) return fail(FFN_ERR_ARG, "candidate %d outside the canvas", k);
-  for (int a = 0; a < 3; ++a)
-    if (rq->min_boundary_dist[a] < 0) return fail(FFN_ERR_ARG, "min_boundary_dist");
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  const long long t_turn0 = steady_ns();
-  HIP_TRY(lock_.begin(e, c));
-  const int32_t max_id = rq->do_commit ? std::max(rq->max_existing_id, 0) : 0;
-  const int novl = rq->do_commit && overlap_ids && overlap_counts
-                       ? std::max(std::min(max_overlaps, max_id), 0) : 0;
-  rc = ensure_turn(e, (size_t)n, (size_t)max_id + 1, (size_t)novl);
-  if (rc) return rc;
-  const TurnLayout lay(e->turn_ncap, e->turn_hcap, e->turn_ocap);
-  char* ds = static_cast<char*>(e->d_turn);
-  const size_t ncap = e->turn_ncap;
-  auto* d_rec = reinterpret_cast<TurnRecord*>(ds);
-  auto* d_part = reinterpret_cast<unsigned long long*>(ds + lay.o_part);
-  auto* d_flag = reinterpret_cast<int*>(ds + lay.o_flag);
-  auto* d_cseed = reinterpret_cast<float*>(ds + lay.o_flag + 4 * ncap);
-  auto* d_cseg = reinterpret_cast<int32_t*>(ds + lay.o_flag + 8 * ncap);
-  auto* d_ci = reinterpret_cast<size_t*>(ds + lay.o_flag + 12 * ncap);
-  auto* d_hist = reinterpret_cast<unsigned*>(ds + lay.o_hist);
-  if (++e->turn_seq == 0) ++e->turn_seq;
-  // the candidates reach the device without a copy operation: the evaluate kernel reads
-  // the pinned buffer (the call does not return before the turn has run, so one buffer)
-  if (n > 0) std::memcpy(e->h_turn, cand, 12 * (size_t)n);
-  long total = 0;
-  Box b = make_box(c, rq->lo, rq->hi, &total);
-  if (!rq->do_commit) {
-    total = 0;
-    b.n[0] = b.n[1] = b.n[2] = 0;
-  }
-  const long rows = total > 0 ? (long)b.n[0] * b.n[1] : 0;
-  const int xs = row_lanes_log2(b.n[2]);
-  const int nparts = rows > 0 ? turn_grid(rows, xs) : 0;
-  const bool has_commit = rq->do_commit || rq->mark_mode;
-  if (nparts > 0)
-    hipLaunchKernelGGL(turn_count_kernel, dim3(nparts), dim3(256), 0, e->ustream, c->seed,
-                       c->seg, b, rows, xs, rq->segment_threshold, max_id,
-                       max_id < kTurnHistLds ? 1 : 0, d_part, d_hist);
-  if (has_commit)
-    hipLaunchKernelGGL(turn_commit_kernel, dim3(std::max(nparts, 1)), dim3(256), 0,
-                       e->ustream, c->seed, c->seg, b, rows, xs, rq->segment_threshold,
-                       rq->segment_id, (long long)rq->min_segment_size, d_part, nparts,
-                       d_rec, rq->mark_pos[0], rq->mark_pos[1], rq->mark_pos[2],
-                       rq->mark_mode);
-  if (n > 0) {
-    hipLaunchKernelGGL(turn_eval_kernel, dim3(n), dim3(64), 0, e->ustream, c->seed,
-                       c->seg, c->cz, c->cy, c->cx,
-                       reinterpret_cast<const int32_t*>(e->h_turn_dev),
-                       rq->min_boundary_dist[0], rq->min_boundary_dist[1],
-                       rq->min_boundary_dist[2], d_flag, d_cseed, d_cseg, d_ci,
-                       c->restrict_planes, c->restrict_plane_words, c->restrict_row_words);
-    // pick, and init_seed at the one picked: the dirty box (or, from half the volume on,
-    // everything) back to NaN and the seed point, in the same launch
-    long dirty_total = 0;
-    Box db = make_box(c, c->dirty_lo, c->dirty_hi, &dirty_total);
-    if (!rq->do_init || c->dirty_lo[0] >= c->dirty_hi[0] || dirty_total <= 0) {
-      dirty_total = 0;
-      db.n[0] = db.n[1] = db.n[2] = 0;
-    }
-    const long drows = dirty_total > 0 ? (long)db.n[0] * db.n[1] : 0;
-    const int dxs = row_lanes_log2(db.n[2]);
-    const int clear = !rq->do_init ? 0 : (size_t)dirty_total * 2 >= c->nvox ? 2 : 1;
-    const int grid = clear == 2 ? 2048 : clear == 1 ? turn_grid(drows, dxs) : 1;
-    uint32_t init_bits;
-    std::memcpy(&init_bits, &rq->init_value, 4);
-    hipLaunchKernelGGL(turn_pick_clear_kernel, dim3(grid), dim3(256), 0, e->ustream,
-                       reinterpret_cast<uint32_t*>(c->seed), c->seg, d_flag, d_ci, n,
-                       d_rec, db, drows, dxs, clear, c->nvox, init_bits);
-  }
-  hipLaunchKernelGGL(turn_publish_kernel, dim3(1), dim3(1024), 0, e->ustream, d_rec,
-                     d_part, 0, d_hist, max_id, novl, d_flag, d_cseed, d_cseg, n,
-                     has_commit ? 1 : 0, n > 0 ? 1 : 0, e->h_turn_dev + lay.w_pub,
-                     e->turn_seq);
-  HIP_TRY(hipGetLastError());
-  const long long t_turn1 = steady_ns();
-  const TurnPub pub{e->h_turn + lay.w_pub, e->turn_seq, (size_t)n};
-  HIP_TRY(lock_.wait_published(e, c, [&] { return pub.arrived(); }));
-  e->turn_hist_clean = true;
-  e->stat_segturn_queue_ns += t_turn1 - t_turn0;
-  e->stat_segturn_wait_ns += steady_ns() - t_turn1;
-  e->stat_segturn_calls += 1;
-  std::memset(out, 0, sizeof(*out));
-  out->counts.raw_segmented_voxels = (int64_t)(pub.at(0) | (uint64_t)pub.at(1) << 32);
-  out->counts.actual_segmented_voxels = (int64_t)(pub.at(2) | (uint64_t)pub.at(3) << 32);
-  out->committed = (int32_t)pub.at(4);
-  out->chosen = (int32_t)pub.at(5);
-  out->counts.num_overlapped_ids = pub.overlaps(overlap_ids, overlap_counts);
-  if (n > 0) {
-    for (int k = 0; k < n; ++k) {
-      cand_flags[k] = (int32_t)pub.at(8 + (size_t)k);
-      const uint32_t sb = pub.at(8 + (size_t)n + k);
-      std::memcpy(&cand_seed[k], &sb, 4);
-      cand_seg[k] = (int32_t)pub.at(8 + 2 * (size_t)n + k);
-    }
-    if (rq->do_init && out->chosen >= 0) {
-      // as ffn_canvas_init_seed: the volume is clean but for the seed point
-      const int32_t* p = cand + 3 * out->chosen;
-      const int lo[3] = {p[0], p[1], p[2]};
-      const int hi[3] = {p[0] + 1, p[1] + 1, p[2] + 1};
-      c->dirty_lo[0] = c->dirty_hi[0] = 0;
-      c->mark_dirty(lo, hi);
-    }
-  }
-  return FFN_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-template <typename T>
-int box_read(ffn_canvas* c, const T* vol, const int32_t lo[3], const int32_t hi[3],
-             T* dst) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !lo || !hi || !dst) return fail(FFN_ERR_ARG, "null argument");
-  int rc = check_box(c, lo, hi);
-  if (rc) return rc;
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  long total;
-  Box b = make_box(c, lo, hi, &total);
-  if (total == 0) return FFN_OK;
-  if (total == (long)c->nvox) {  // whole volume: straight (blocking) copy
-    HIP_TRY(canvas_quiesce(e, c));
-    HIP_TRY(hipMemcpy(dst, vol, sizeof(T) * total, hipMemcpyDeviceToHost));
-    return FFN_OK;
-  }
-  HIP_TRY(lock_.begin(e, c));
-  rc = ensure_scratch(e, sizeof(T) * total);
-  if (rc) return rc;
-  hipLaunchKernelGGL((box_read_kernel<T>), dim3(grid_for(total)), dim3(256), 0,
-                     e->ustream, vol, b, total, static_cast<T*>(e->d_scratch));
-  HIP_TRY(hipMemcpyAsync(e->h_scratch, e->d_scratch, sizeof(T) * total,
-                         hipMemcpyDeviceToHost, e->ustream));
-  HIP_TRY(lock_.wait(e, c));
-  std::memcpy(dst, e->h_scratch, sizeof(T) * total);
-  return FFN_OK;
-}
-
-template <typename T>
-int box_write(ffn_canvas* c, T* vol, const int32_t lo[3], const int32_t hi[3],
-              const T* src) {
-  UtilLock lock_(c ? c->engine : nullptr);
-  if (!c || !lo || !hi || !src) return fail(FFN_ERR_ARG, "null argument");
-  int rc = check_box(c, lo, hi);
-  if (rc) return rc;
-  ffn_engine* e = c->engine;
-  if (!e) return fail(FFN_ERR_STATE, "canvas outlived its engine");
-  HIP_TRY(hipSetDevice(e->device));
-  long total;
-  Box b = make_box(c, lo, hi, &total);
-  if (total == 0) return FFN_OK;
-  if (total == (long)c->nvox) {  // whole volume: straight (blocking) copy
-    HIP_TRY(canvas_quiesce(e, c));
-    HIP_TRY(hipMemcpy(vol, src, sizeof(T) * total, hipMemcpyHostToDevice));
-    return FFN_OK;
-  }
-  HIP_TRY(lock_.begin(e, c));
-  rc = ensure_scratch(e, sizeof(T) * total);
-  if (rc) return rc;
-  std::memcpy(e->h_scratch, src, sizeof(T) * total);
-  HIP_TRY(hipMemcpyAsync(e->d_scratch, e->h_scratch, sizeof(T) * total,
-                         hipMemcpyHostToDevice, e->ustream));
-  hipLaunchKernelGGL((box_write_kernel<T>), dim3(grid_for(total)), dim3(256), 0,
-                     e->ustream, vol, b, total,
-                     static_cast<const T*>(e->d_scratch));
-  HIP_TRY(lock_.wait(e, c));
-  return FFN_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ffn_canvas_read_seed(ffn_canvas* c, const int32_t lo[3], const int32_t hi[3],
-                         float* dst) {
-  return box_read<float>(c, c ? c->seed : nullptr, lo, hi, dst);
-}
-
-int ffn_canvas_read_segmentation(ffn_canvas* c, const int32_t lo[3],
-                                 const int32_t hi[3], int32_t* dst) {
-  return box_read<int32_t>(c, c ? c->seg : nullptr, lo, hi, dst);
-}
-
-int ffn_canvas_write_seed(ffn_canvas* c, const int32_t lo[3], const int32_t hi[3],
-                          const float* src) {
-  if (c && lo && hi) c->mark_dirty(lo, hi);
-  return box_write<float>(c, c ? c->seed : nullptr, lo, hi, src);
-}
-
-int ffn_canvas_write_segmentation(ffn_canvas* c, const int32_t lo[3],
-                                  const int32_t hi[3], const int32_t* src) {
-  return box_write<int32_t>(c, c ? c->seg : nullptr, lo, hi, src);
 }
 
 }  // extern "C"

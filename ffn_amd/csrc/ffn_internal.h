@@ -3,7 +3,8 @@
 #define FFN_INTERNAL_H_
 
 // Stores a printf-formatted message for ffn_last_error() (thread local) and
-// returns `code`.  Defined in ffn_hip.hip.
+// returns `code`.  Defined in ffn_hip.hip, next to ffn_last_error(); the engine's own
+// units call it as fail() (ffn_engine.h).
 int ffn_set_error(int code, const char* fmt, ...)
     __attribute__((format(printf, 2, 3)));
 

@@ -1,5 +1,5 @@
 // The kernels around the conv stack of a FoV step: gather + conv0_a in front of it, head / faces / paste / the fused step launches behind it.
-// (part of ffn_kernels.h: included from there, in this order, inside no namespace)
+// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {
@@ -99,8 +99,7 @@ typedef _Float16 f16x4_c0 __attribute__((ext_vector_type(4)));
 // later (ffn_step_result.cand_seed / cand_seg) and then queues the rest of the
 // step behind this launch; `choice` (-1: none valid, nothing computed) lets the
 // step's faces kernel verify that both chose the same position.
-constexpr int kSpecMax = 3;
-struct SpecArgs {
+struct SpecArgs {  // (kSpecMax: ffn_types.h)
   int n;                 // 0: a normal launch at si's request position
   int pos[kSpecMax][3];  // zyx
   float move_thr;

@@ -141,7 +141,10 @@ void ffn_engine_destroy(ffn_engine* engine);
 /* Replaces tf.train.Saver().restore (runner.py:98-111).  `blob` holds the TF
  * variables in graph order, each tensor exactly as TensorFlow stores it:
  *   conv0_a W[3][3][3][2][F] b[F], conv0_b W[3][3][3][F][F] b[F],
- *   conv{i}_a W b, conv{i}_b W b  (i = 1..depth-1), conv_lom W[F] b[1].     */
+ *   conv{i}_a W b, conv{i}_b W b  (i = 1..depth-1), conv_lom W[F] b[1].
+ * Cost: the repack and upload, plus -- where the resident launch is in use and
+ * "flow_pace" is at its default (ffn_hip_debug.h) -- a measurement of that
+ * launch's beat, ~0.3 s once per (device, depth, FoV) and process.           */
 int ffn_engine_set_weights(ffn_engine* engine, const float* blob, size_t count);
 size_t ffn_engine_weight_count(int depth, int features);
 
@@ -404,110 +407,56 @@ int ffn_engine_get_profile_samples(ffn_engine* engine, float* out_ms, int max_n,
  * ffn_predict still returns the whole FoV (the caller crops).  pred_zyx = the
  * FoV: back to the default.  Deltas must fit the box's half size. */
 int ffn_engine_set_pred_size(ffn_engine* engine, const int32_t pred_zyx[3]);
-/* Kernel choice and tuning switches.  "conv_variant":
- *   0 = simple exact-f32 MFMA conv over padded positions (takes any FoV that
- *       fits the LDS at all),
- *   2 = exact-f32 MFMA conv over compact chunks, pipelined, K-split middle tile
- *       (bitwise the oracle's fmaf chain),
+/* ---- options --------------------------------------------------------------
+ * The options a user sets; none but "conv_variant" changes a result beyond f32
+ * summation order.  The lab's options (pacing, ablation, tracing, "stat_*"
+ * counters) and the debug readers are in ffn_hip_debug.h.  An out-of-range value
+ * or an unknown name is FFN_ERR_ARG.
+ * "conv_variant": the kernel of the 32->32 convs:
+ *   0 = simple exact-f32 MFMA conv over padded positions (any FoV that fits the LDS),
+ *   2 = exact-f32 MFMA conv over compact chunks, pipelined (bitwise the oracle's
+ *       fmaf chain),
  *   6 = conv32d: every f32 product carried as 3 fp16 products (hi + 2^-11 *
  *       residual: 22 mantissa bits, about the rounding noise of an f32 GEMM) on
- *       32x32x16 MFMAs, the 27 taps split over 4 waves, producer-split fp16
- *       planes staged by LDS-DMA; operands must stay inside the fp16 range,
- *       else FFN_ERR_RANGE,
+ *       32x32x16 MFMAs; operands must stay inside the fp16 range, else
+ *       FFN_ERR_RANGE,
  *   7 = 6 in 96-voxel chunks (two workgroups per CU; the same bits),
- *   8 = conv32m: the same products, M split over the waves, weights through an
- *       LDS-DMA ring, two workgroups per CU,
+ *   8 = conv32m: the same products, M split over the waves, two workgroups per CU,
  *   9 (default where the FoV has 257 .. 512 chunks of 128 voxels, e.g. 33^3) =
  *       a step of ONE FoV runs conv32mt (conv32m for the first 256 chunks +
  *       32-voxel K-split tail workgroups), a step of several runs conv32m,
- *  10 = a step of ONE FoV on 80-voxel workgroups, two per CU (conv32hs / conv32h:
- *       four 16-position tiles on 16x16x32 MFMAs + a fifth tile split over the
- *       waves by tap; another summation order than 9, the same tolerance); a step
- *       of several FoVs runs conv32m as under 9.  Measured SLOWER than 9 at 33^3
- *       (profiles/r06_gate_two_chains.txt): selectable, not a default,
- *  -1 = this FoV's exact-f32 kernel ("exact_variant": 2 where it fits, else 0).
- * (1, 3, 4, 5 -- conv32p, the bf16x3 and the earlier fp16 kernels -- were removed
- * in ABI 7; they are in the history up to commit af82310.)
- * "tail_batched" 1 = conv32mt for every step (one arithmetic whatever the
- * batch); "batch_chunks" (variant 6): the form batched steps take.  Results
- * are identical up to f32 summation order.  "fuse_head" (variant 2): 1x1x1
- * head inside the last conv launch.  "store_policy" (variant 2): 0 write-back,
- * 1 write-through, 2 non-temporal conv stores.
- * "speculate" (default 1): single-FoV steps made by ffn_canvas_segment_at queue
- * conv0_a of the NEXT step behind their paste, for the positions the segment
- * loop expects to pop next (the kernel takes the first that passes
- * Canvas.is_valid_pos on the pasted canvas; the host makes the same choice from
- * the step result and then queues the rest of the step behind it; a step whose
- * launch chose otherwise pastes nothing and is made again).  "fuse_paste"
- * (default 1): faces and paste of a single-FoV step as one launch; "fuse_conv0a"
- * (default 1): ... and the next step's conv0_a in it as well.  "stack_ahead"
- * (default 1): the resident conv stack of that next step is queued right behind the
- * launch that holds its conv0_a, before the host has seen this step's record -- the
- * host's turn-around and the launch latency leave the step's critical path (the stack
- * reads only what that conv0_a wrote; if the device found no valid position it ends
- * after its first conv and the step is made the ordinary way).  "paste_blocks" (0 =
- * automatic: one block per compute unit in the fused step launch).  None changes any
- * result.  "debug_submit_delay_ns": the host idles this long in front of every step's
- * launches (an experiment: what a slower host costs with and without stack_ahead);
- * "debug_fused_twice": the fused step launch is made twice (idempotent), so that a trace of
- * the second shows what warm caches are worth (nothing: profiles/r06_turn_around.txt).
- * "flow": how the 2 depth - 1 convs of a single-FoV step of conv_variant 9 run:
- *   0 = one dependent launch per conv, 1 = the same launches with the flagged
+ *  10 = a step of ONE FoV on 80-voxel workgroups, two per CU (conv32hs / conv32h;
+ *       another summation order than 9, the same tolerance).  Measured SLOWER than
+ *       9 at 33^3 (profiles/r06_gate_two_chains.txt): selectable, not a default,
+ *  -1 = this FoV's exact-f32 kernel ("exact_variant", read-only: 2 where it fits,
+ *       else 0).
+ *   (1, 3, 4, 5 were removed in ABI 7; they are in the history up to af82310.)
+ * "flow" 0..2: how the 2 depth - 1 convs of a single-FoV step of conv_variant 9
+ *   run: 0 = one dependent launch per conv, 1 = the same launches with the flagged
  *   hand-off compiled in, 2 = ONE resident launch whose workgroups hand rows to
  *   each other (conv32ps) -- bit-identical in every mode.  2 is the default where
  *   the device can hold all of the launch's workgroups at once (checked at
- *   ffn_engine_create: compute units x occupancy >= grid; else 0, and setting 2
- *   is FFN_ERR_ARG).  A resident launch that times out waiting for one of its
- *   own workgroups voids its step with FFN_ERR_FLOW (see above); after three such
- *   steps in a row the engine sets "flow" = 0 itself ("flow_auto_off" reads 1;
- *   setting "flow" again re-arms).  "flow_debug" 2048: fault injection for
- *   tests (a producer stops publishing); its other bits and "debug_clock" 4 act
- *   only in -DFFN_EXPERIMENTS=1 builds.
- * "flow_pace": the beat of the resident launch, in 10-ns ticks: conv l of a
- *   workgroup does not start before t0 + l x beat + "flow_pace_spread" x (its first
- *   voxel / V).  -1 (default) = the beat ffn_engine_set_weights MEASURED for this
- *   device (a ladder of beats on noise inputs, ~80 ms; 0 if none beats the
- *   free-running launch by 1.5 %), 0 = free-running, > 0 = that beat;
- *   "flow_pace_spread" -1 (default) = as wide as the beat.  Timing only: results are
- *   bit-identical under any beat (profiles/r06_pacing.txt).
- * "debug_fused_trace" N: the N-th next single-FoV step stamps when each role of its
- *   two launches ran ("debug_fused_stamp_4" .. "_27", 10-ns ticks after the stack's
- *   first workgroup -- under stack_ahead after the entry of the step's faces block:
- *   tools/gpu_step_trace.py names the slots). */
+ *   ffn_engine_create; else 0, and setting 2 is FFN_ERR_ARG).  A resident launch
+ *   that times out voids its step with FFN_ERR_FLOW (see above); after three such
+ *   steps in a row the engine sets "flow" = 0 itself ("flow_auto_off", read-only,
+ *   reads 1; setting "flow" again re-arms).
+ * "batch_chunks" 0..2 (variant 6): the form steps of several FoVs take;
+ * "tail_batched" 1 = conv32mt for every step (one arithmetic whatever the batch).
+ * "speculate" (default 1): single-FoV steps of the segment loop queue conv0_a of the
+ *   NEXT step behind their paste, for the positions the loop expects to pop next; a
+ *   step whose launch chose another position pastes nothing and is made again.
+ * "stack_ahead" (default 1): ... and that step's resident conv stack right behind
+ *   it, before the host has seen this step's record.
+ * "fuse_paste" (default 1): faces and paste of a single-FoV step as one launch;
+ * "fuse_conv0a" (default 1): the next step's conv0_a in it as well; "fuse_head"
+ *   (variant 2): the 1x1x1 head inside the last conv launch.
+ * "store_policy" 0..2 (variant 2): write-back, write-through, non-temporal stores.
+ * "sync_mode": 1 (default) = a step's wait polls its record in pinned memory,
+ *   0 = it blocks on the stream.  "profile_every" N >= 1: the profiler samples one
+ *   of every N conv stacks. */
 int ffn_engine_set_option(ffn_engine* engine, const char* name, int value);
-/* Current value of an option ("conv_variant", "exact_variant", "fuse_head",
- * "store_policy", "sync_mode", "profile_every", "speculate", "fuse_paste",
- * "fuse_conv0a", "stack_ahead", "paste_blocks", "flow", "flow_auto_off", "flow_pace", "flow_pace_now" (the beat in
- * use), "flow_pace_free_ns" / "flow_pace_best_ns" (what the measurement saw per
- * stack: free-running, at its best beat)), "stat_flow_timeouts" (polls of the
- * resident launch that gave up, ever) / "stat_flow_voids" (steps voided by one),
- * "stat_turn_gpu_ns" / "stat_turn_host_ns" / "stat_launch_host_ns" / "stat_turn_count"
- * (between two single-FoV steps inside a segment, mean since "stat_reset": record
- * published -> first instruction of the next resident launch as the GPU saw it;
- * record seen -> that launch queued, and the launch call alone, on the host), or
- * a statistic of the step calls since set_option("stat_reset", 0):
- * "stat_step_calls", "stat_step_items" (FoVs in them), "stat_hist_<n>" (calls
- * with n FoVs), "stat_spec_launched" / "stat_spec_hits" / "stat_spec_mismatch"
- * (conv0_a launches made ahead, steps that ran on one, steps repeated),
- * "stat_ahead_used" / "stat_ahead_wasted" (stacks queued ahead that their step used /
- * that no step used). */
+/* Current value of an option that set_option takes, or of a read-only one. */
 int ffn_engine_get_option(ffn_engine* engine, const char* name, int* value);
-/* Debug: with option "debug_clock" = 1 the compact conv kernel records, for its
- * first workgroup, per wave {shader clock at entry, at main-loop start, at
- * main-loop end, at exit, wall clock (100 MHz) at entry, at exit}. */
-int ffn_engine_debug_clocks(ffn_engine* engine, long long* out24);
-/* Debug: with "debug_clock" = 2 every workgroup of the conv32m / conv32mt launch
- * of layer "debug_layer" also records {wall clock (100 MHz) at entry, at exit,
- * HW_ID, XCC_ID}: out[4 b ..] for blockIdx b < max_wgs <= 4096 (zeros for a
- * block that exited at once).  Clears the records. */
-int ffn_engine_debug_workgroups(ffn_engine* engine, long long* out, int max_wgs);
-/* Debug: with "debug_clock" = 4 every workgroup of a FLOW conv (option "flow" 1
- * or 2: the resident stack of a single-FoV step) records per conv of the stack
- * six wall-clock stamps (100 MHz): body entry, input tiles seen, first segment
- * landed, tap loop over, stores drained, tiles published.
- * out[(slot * 64 + conv) * 8 + 0..5] for workgroup slot < max_slots (main chunks
- * first, then the tail chunks).  Clears the records. */
-int ffn_engine_debug_flow_trace(ffn_engine* engine, long long* out, int max_slots);
 /* Blocks until all work queued on the engine's stream has finished. */
 int ffn_engine_synchronize(ffn_engine* engine);
 
