@@ -442,7 +442,11 @@ SIGNATURES = {
     'ffn_optimizer_apply': (_I, [_P, _I, ctypes.c_int64, _P, _P, _P, _P,
                                  ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_float]),
+    'ffn_optimizer_aggregate': (_I, [_P, ctypes.c_int64, _I, _P,
+                                     ctypes.c_int64, ctypes.c_float, _P]),
     'ffn_optimizer_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
+    'ffn_optimizer_last_timing_aggregate': (
+        _I, [_P, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -11,6 +11,12 @@
 // definition is rounded on its own, so the result equals a restatement with
 // one numpy f32 operation per written operation.
 //
+// aggregate_kernel has the same shape: one launch, a grid-stride loop over
+// 16-byte vectors, the tail by the first threads.  A thread folds the n
+// replica arrays of its vector in replica order (the loads of a vector's
+// replicas are independent of the sum and are issued ahead of it, four at a
+// time), divides once and stores once.  No LDS, no atomics.
+//
 // stats_kernel takes per-thread maxima and counts, an LDS tree per workgroup,
 // and writes one partial per workgroup; stats_sum_kernel (one workgroup)
 // combines them.  A maximum and integer sums are the same in any order.
@@ -39,6 +45,7 @@ constexpr int kThreads = 256;
 constexpr int kApplyBlocks = 512;  // at most: two workgroups a CU
 constexpr int kStatBlocks = 256;   // at most: what stats_sum_kernel reads
 constexpr int kRules = 5;
+constexpr int kMaxReplicas = 256;  // arrays one aggregate folds
 
 struct Coef {
   float lr, clip, c0, c1, eps;
@@ -139,6 +146,47 @@ __global__ __launch_bounds__(kThreads) void apply_kernel(
   }
 }
 
+// One entry of a replica's gradient, clipped as `update` clips.
+__device__ __forceinline__ float clipped(float g, float clip) {
+  if (clip > 0.f) {
+    g = g < -clip ? -clip : g;
+    g = g > clip ? clip : g;
+  }
+  return g;
+}
+
+// dst[i] = (clip(src[0][i]) + clip(src[1][i]) + ... in this order) / n, the
+// definition of aggregate in ffn_optimizer.h.  stride: floats between arrays.
+__global__ __launch_bounds__(kThreads) void aggregate_kernel(
+    const float* __restrict__ src, long long stride, int n, int count,
+    float clip, float* __restrict__ dst) {
+  const int nvec = count >> 2;
+  const int tid = blockIdx.x * kThreads + threadIdx.x;
+  const int step = gridDim.x * kThreads;
+  const float fn = (float)n;
+  for (int i = tid; i < nvec; i += step) {
+    f32x4 t = reinterpret_cast<const f32x4*>(src)[i];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) t[c] = clipped(t[c], clip);
+#pragma unroll 4
+    for (int r = 1; r < n; ++r) {
+      const f32x4 g = reinterpret_cast<const f32x4*>(src + r * stride)[i];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) t[c] = t[c] + clipped(g[c], clip);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) t[c] = t[c] / fn;
+    reinterpret_cast<f32x4*>(dst)[i] = t;
+  }
+  // the count % 4 elements behind the last whole vector
+  const int e = (nvec << 2) + tid;
+  if (tid < 4 && e < count) {
+    float t = clipped(src[e], clip);
+    for (int r = 1; r < n; ++r) t = t + clipped(src[r * stride + e], clip);
+    dst[e] = t / fn;
+  }
+}
+
 struct Stats {
   float max_abs;
   u64 clipped, nonfinite;
@@ -226,7 +274,7 @@ struct ffn_optimizer : ffn_unit::Unit {
   DevBuf counts;  // kStatBlocks x 2 partial counts + the 3 results
   DevBuf maxima;  // kStatBlocks partial maxima
   PinnedBuf stage;
-  double ms[2] = {0, 0};
+  double ms[3] = {0, 0, 0};  // grad_stats, apply, aggregate
 };
 
 namespace {
@@ -386,10 +434,43 @@ int ffn_optimizer_apply(ffn_optimizer* h, int rule, int64_t count,
   return end(h, 1);
 }
 
+int ffn_optimizer_aggregate(ffn_optimizer* h, int64_t count, int n,
+                            const float* src_dev, int64_t stride, float clip,
+                            float* dst_dev) {
+  U_OK(check_count(h, count));
+  if (n < 1 || n > kMaxReplicas)
+    return ffn_set_error(FFN_ERR_ARG, "n = %d, expected 1 .. %d", n,
+                         kMaxReplicas);
+  O_PTR(src_dev);
+  O_PTR(dst_dev);
+  if (stride < count || stride % 4 != 0)
+    return ffn_set_error(FFN_ERR_ARG,
+                         "stride = %lld, expected a multiple of 4 that is >= "
+                         "count = %lld", (long long)stride, (long long)count);
+  U_OK(check_aligned(src_dev, "src_dev"));
+  U_OK(check_aligned(dst_dev, "dst_dev"));
+  // (n - 1) * stride + count < 2^8 * 2^31: no overflow of size_t
+  const size_t span = (size_t)(n - 1) * (size_t)stride + (size_t)count;
+  if (src_dev < dst_dev + count && dst_dev < src_dev + span)
+    return ffn_set_error(FFN_ERR_ARG, "dst_dev overlaps src_dev");
+  if (std::isnan(clip)) return ffn_set_error(FFN_ERR_ARG, "clip is a NaN");
+  U_OK(begin(h));
+  hipLaunchKernelGGL(aggregate_kernel, dim3(blocks_for(count, kApplyBlocks)),
+                     dim3(kThreads), 0, h->stream, src_dev, (long long)stride,
+                     n, (int)count, clip, dst_dev);
+  return end(h, 2);
+}
+
 int ffn_optimizer_last_timing(ffn_optimizer* h, double kernel_ms[2]) {
   if (!h || !kernel_ms) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
   kernel_ms[0] = h->ms[0];
   kernel_ms[1] = h->ms[1];
+  return FFN_OK;
+}
+
+int ffn_optimizer_last_timing_aggregate(ffn_optimizer* h, double* kernel_ms) {
+  if (!h || !kernel_ms) return ffn_set_error(FFN_ERR_ARG, "NULL argument");
+  *kernel_ms = h->ms[2];
   return FFN_OK;
 }
 

@@ -94,6 +94,11 @@ class BatchExampleIter:
     own generator, and the example is loaded with EvaluationOps.load_sections.
     Coordinates whose patches enlarged by the margin leave their volume are
     skipped.  None: load_augmented, as before.
+  result: an evaluation.EvalResult to score into instead of one of the
+    iterator's own, so the iterators of several replicas of one process
+    accumulate into one (it must have been made for the same shifts in the same
+    order); `reset_result(result)` hands every one of them the next.  None: an
+    EvalResult of its own, as before.
   keep_history: keep, per example started, its coordinate index, transform,
     offsets and records (and its section plan under 'plan') in `history`
     (tests; it grows without bound).
@@ -104,7 +109,7 @@ class BatchExampleIter:
                seed_pad: float = 0.05, shifts: Optional[Sequence] = None,
                shuffle_moves: bool = False, moves_seed: Optional[int] = None,
                transform=None, shuffle_seed: Optional[int] = None, io=None,
-               keep_history: bool = False, sections=None):
+               keep_history: bool = False, sections=None, result=None):
     if fov_policy not in TRAIN_POLICIES:
       raise ValueError('fov_policy is one of %r, got %r' %
                        (TRAIN_POLICIES, fov_policy))
@@ -185,13 +190,16 @@ class BatchExampleIter:
     self.examples_started = 0
     self.examples_finished = 0
     self.steps = 0
-    self.result = evaluation.EvalResult(self.shifts)
+    self.result = (result if result is not None
+                   else evaluation.EvalResult(self.shifts))
 
   # -- bookkeeping ---------------------------------------------------------------
 
-  def reset_result(self):
-    """EvalTracker.reset: a fresh `result` for the next summary interval."""
-    self.result = evaluation.EvalResult(self.shifts)
+  def reset_result(self, result=None):
+    """EvalTracker.reset: a fresh `result` for the next summary interval (or
+    the given one, shared with other iterators)."""
+    self.result = (result if result is not None
+                   else evaluation.EvalResult(self.shifts))
 
   def _count_sections(self, plan):
     summary = plan.summary()

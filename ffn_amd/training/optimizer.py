@@ -2,12 +2,14 @@
 
 `OptimizerOps` is the handle over the optimizer unit of libffn_hip.so
 (include/ffn_optimizer.h): gradient statistics and the clipped update of one
-of five rules over flat f32 device arrays, one launch for all elements.
+of five rules over flat f32 device arrays, one launch for all elements, and
+`aggregate`, the clipped mean of the gradients of n replicas in replica order.
 
 `OptimizerConfig` mirrors the flags of reference ffn/training/optimizer.py and
 model.py:127 with their defaults, and owns the learning-rate schedule
 (optimizer.py:80-86: exponential decay, staircase).  sync_sgd and the replica
-flags are not taken.
+flags are train.py's and the trainer's (trainer.ConvStackTrainer.contribute,
+apply_contributions), not this class's.
 
 The arena layout (`arena_layout`, `pack`, `unpack`) says where each variable of
 a conv stack lies in the flat arrays a trainer hands to the unit; it is plain
@@ -81,12 +83,29 @@ class OptimizerOps(_unit.Handle):
           _addr(slot0), _addr(slot1), float(lr), float(clip), float(c0),
           float(c1), float(eps)))
 
+  def aggregate(self, count, n, src, stride, clip, dst):
+    """dst = the mean of the `n` arrays of `count` floats that lie `stride`
+    floats apart in `src`, each clipped first, folded in the order they lie
+    (ffn_optimizer.h's definition: the gradients of n replicas)."""
+    with self.lock:
+      check(self._lib.ffn_optimizer_aggregate(
+          self._h, int(count), int(n), _addr(src), int(stride), float(clip),
+          _addr(dst)))
+
   def last_timing(self):
     """{call name: HIP-event kernel ms of its last run on this handle}."""
     ms = (ctypes.c_double * len(TIMED_CALLS))()
     with self.lock:
       check(self._lib.ffn_optimizer_last_timing(self._h, ms))
     return dict(zip(TIMED_CALLS, [float(v) for v in ms]))
+
+  def last_timing_aggregate(self) -> float:
+    """HIP-event kernel ms of the last aggregate on this handle."""
+    ms = ctypes.c_double(0.0)
+    with self.lock:
+      check(self._lib.ffn_optimizer_last_timing_aggregate(
+          self._h, ctypes.byref(ms)))
+    return float(ms.value)
 
 
 _default = _unit.Registry(OptimizerOps)

@@ -52,6 +52,25 @@
  * clip <= 0), nonfinite = the number of NaN or +-inf entries.  A maximum and
  * integer sums do not depend on the order they are taken in: per-workgroup
  * partials, combined by a second launch.  No float atomics.
+ *
+ * Exact definition of aggregate: the gradients of n replicas, each clipped,
+ * folded in replica order and averaged.  src holds n arrays of `count` floats,
+ * `stride` floats apart (array r starts at src + r * stride).  Per element i,
+ * in f32, every operation IEEE-rounded (to nearest even) on its own and in the
+ * order written; no fused multiply-add, / is the correctly rounded one, and
+ * denormals are kept:
+ *   c_r = src[r * stride + i];  if clip > 0:  c_r < -clip -> -clip,
+ *                                              c_r > clip -> clip
+ *   (a NaN stays a NaN, -0 stays -0)
+ *   t = c_0
+ *   t = t + c_r            for r = 1 .. n - 1, in this order
+ *   dst[i] = t / (float)n
+ * n = 1 gives dst = clip(src) / 1.0f, which keeps the bits of the clipped
+ * value, a -0 included.  The order of the fold is part of the contract: f32
+ * addition is not associative, and a caller that gathers replica gradients
+ * from several processes gets the same bits whatever dealt the replicas to
+ * the processes, as long as it lays them out in replica order
+ * (tests/replicas_ref.py restates the fold in numpy).  One launch, no atomics.
  */
 #ifndef FFN_OPTIMIZER_H_
 #define FFN_OPTIMIZER_H_
@@ -89,9 +108,20 @@ int ffn_optimizer_apply(ffn_optimizer* h, int rule, int64_t count,
                         float* slot0_dev, float* slot1_dev, float lr,
                         float clip, float c0, float c1, float eps);
 
+/* 1 <= n <= 256; stride >= count and a multiple of 4 (every array is 16-byte
+ * aligned); dst_dev (count floats) must not overlap the (n - 1) * stride +
+ * count floats of src_dev; clip must not be a NaN.  src is only read. */
+int ffn_optimizer_aggregate(ffn_optimizer* h, int64_t count, int n,
+                            const float* src_dev, int64_t stride, float clip,
+                            float* dst_dev);
+
 /* HIP-event kernel time of the last grad_stats (index 0) and the last apply
  * (1) on this handle. */
 int ffn_optimizer_last_timing(ffn_optimizer* h, double kernel_ms[2]);
+
+/* The third entry of the unit's timing, of the last aggregate.  (A call of
+ * its own: last_timing's array of two is what existing callers allocate.) */
+int ffn_optimizer_last_timing_aggregate(ffn_optimizer* h, double* kernel_ms);
 
 #ifdef __cplusplus
 }

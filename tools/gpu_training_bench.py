@@ -14,8 +14,14 @@ apply's effective bandwidth: the bytes the rule must move -- params and
 gradients read, params written, every slot read and written, 4 bytes each --
 over the kernel time.  One JSON line per batch size and per rule.
 
+Synchronous replicas: the HIP-event kernel time of aggregate over the arena
+at 2, 8 and 32 replicas (and the bandwidth of n arrays read, one written), and
+the wall time of a step of two local replicas (two contribute, one
+apply_contributions) against two plain train steps at batch 4.  One process
+on one GPU: no collective runs here.
+
   python tools/gpu_training_bench.py [--batches 1 8 16] [--repeats 10]
-      [--weights tests/golden/fib25_weights.npz]
+      [--weights tests/golden/fib25_weights.npz] [--only_replicas]
 """
 import argparse
 import json
@@ -57,6 +63,11 @@ def main():
                   help='.npz keyed by the checkpoint\'s variable names '
                   '(default: random weights)')
   ap.add_argument('--device', type=int, default=0)
+  ap.add_argument('--aggregate', type=int, nargs='*', default=[2, 8, 32],
+                  help='replica counts of the aggregate part')
+  ap.add_argument('--replica_batch', type=int, default=4)
+  ap.add_argument('--only_replicas', action='store_true',
+                  help='the aggregate part alone')
   args = ap.parse_args()
 
   zyx = tuple(args.fov)
@@ -67,6 +78,10 @@ def main():
   else:
     model.init_random(stddev=0.05)
   import torch  # pylint:disable=g-import-not-at-top
+
+  if args.only_replicas:
+    replicas_part(args, model, zyx)
+    return
 
   for n in args.batches:
     csg = gradients.ConvStackGradients(model, n, args.device)
@@ -126,6 +141,66 @@ def main():
     tr.close()
     del tr
     torch.cuda.empty_cache()
+  replicas_part(args, model, zyx)
+
+
+def replicas_part(args, model, zyx):
+  """The aggregate kernel over the arena at n replicas, and a step of two
+  local replicas against two plain steps."""
+  import torch  # pylint:disable=g-import-not-at-top
+  ops = optimizer.OptimizerOps(args.device)
+  total = optimizer.arena_layout(args.depth).total
+  device = torch.device('cuda', args.device)
+  for n in args.aggregate:
+    src = torch.randn((n, total), dtype=torch.float32, device=device) * 0.5
+    dst = torch.empty((total,), dtype=torch.float32, device=device)
+    torch.cuda.synchronize()
+    ops.aggregate(total, n, src, total, 0.7, dst)  # warm-up
+    ms = []
+    for _ in range(args.repeats):
+      ops.aggregate(total, n, src, total, 0.7, dst)
+      ms.append(ops.last_timing_aggregate())
+    moved = 4 * total * (n + 1)
+    print(json.dumps({
+        'aggregate_replicas': n, 'elements': total,
+        'aggregate_kernel_ms': spread(ms),
+        'aggregate_effective_GBps_at_median': round(
+            moved / (statistics.median(ms) * 1e-3) / 1e9, 1),
+    }), flush=True)
+    del src, dst
+  ops.close()
+  batch = args.replica_batch
+  plain = trainer_lib.ConvStackTrainer(model, optimizer.OptimizerConfig(),
+                                       batch, args.device)
+  two = trainer_lib.ConvStackTrainer(model, optimizer.OptimizerConfig(), batch,
+                                     args.device, replicas=2)
+  dev = [torch.from_numpy(a).to(plain.device) for a in inputs(batch, zyx)]
+  torch.cuda.synchronize()
+  plain.train_step_device(*dev)  # warm-up
+  two.contribute(0, *dev)
+  two.contribute(1, *dev)
+  two.apply_contributions()
+  plain_ms, two_ms = [], []
+  for _ in range(args.repeats):
+    t0 = time.perf_counter()
+    plain.train_step_device(*dev)
+    plain.train_step_device(*dev)
+    plain_ms.append((time.perf_counter() - t0) * 1e3)
+    t0 = time.perf_counter()
+    two.contribute(0, *dev)
+    two.contribute(1, *dev)
+    two.apply_contributions()
+    two_ms.append((time.perf_counter() - t0) * 1e3)
+  print(json.dumps({
+      'batch': batch, 'fov_zyx': list(zyx), 'depth': args.depth,
+      'repeats': args.repeats,
+      'two_plain_steps_wall_ms': spread(plain_ms),
+      'two_replica_step_wall_ms': spread(two_ms),
+      'two_replica_step_over_two_plain_steps': round(
+          statistics.median(two_ms) / statistics.median(plain_ms), 4),
+  }), flush=True)
+  plain.close()
+  two.close()
 
 
 if __name__ == '__main__':

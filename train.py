@@ -40,8 +40,26 @@ examples perturbed, under augmentation/*.  A loss or a
 gradient that is not finite ends the run with InvalidLossError; the last
 checkpoint written stays as it is.
 
-Not here: TensorFlow-format checkpoints, replicas (--master, --task,
---ps_tasks, --replica_step_delay), tf.train.shuffle_batch's queue (the
+With --sync_sgd --replicas_to_aggregate R a step takes R batches of
+--batch_size FoVs (R "replicas", each with its own example stream: coordinates
+r::R of the file, seeds --seed + r), their gradients all under the same
+variables, clips each, averages them in replica order and applies the mean
+once (ConvStackTrainer.contribute / apply_contributions; the reference clips
+before SyncReplicasOptimizer averages, model.py:142-145).  One process hosts
+all R; started by torch.distributed.run, every rank hosts R / world of them
+on its own GPU (--ranks_share_gpus with --collective_backend gloo: on GPU
+local_rank % device_count), the ranks all-gather the raw gradients and every
+rank folds them itself, so the result depends on neither the collective
+library's summation order nor the number of ranks.  The seed is rank 0's;
+every rank resumes from the newest pair in --train_dir; only rank 0 writes
+checkpoints and summaries, whose lines then carry `replicas` and `world`, the
+loss as the mean over all R, and eval/*, moves/* of rank 0's replicas; before
+every checkpoint the ranks compare a checksum of their parameters and stop
+if they differ.  No run on more than one GPU exists yet.
+
+Not here: TensorFlow-format checkpoints, asynchronous replicas (--master,
+--task, --ps_tasks, --replica_step_delay), backup replicas (--total_replicas
+above --replicas_to_aggregate), tf.train.shuffle_batch's queue (the
 coordinates are cycled, reshuffled per epoch), image summaries, the elastic,
 affine, rotation and tf.image contrast augmentations.  TensorFlow's
 random number streams are not reproduced: --seed makes a run of this script
@@ -68,6 +86,7 @@ from ffn_amd.training import augmentation  # noqa: E402
 from ffn_amd.training import evaluation  # noqa: E402
 from ffn_amd.training import examples  # noqa: E402
 from ffn_amd.training import optimizer as optimizer_lib  # noqa: E402
+from ffn_amd.training import replicas as replicas_lib  # noqa: E402
 from ffn_amd.training.import_util import import_symbol  # noqa: E402
 
 CHECKPOINT_RE = re.compile(r'^model\.ckpt-(\d+)\.npz$')
@@ -87,6 +106,16 @@ def _boolean(text):
   if text.lower() in ('false', '0', 'no'):
     return False
   raise argparse.ArgumentTypeError('expected true or false, got %r' % text)
+
+
+def job_environment(environ=None):
+  """(rank, world, local rank, launched) from the environment that
+  torch.distributed.run gives its workers; (0, 1, 0, False) outside one."""
+  environ = os.environ if environ is None else environ
+  if 'RANK' not in environ or 'WORLD_SIZE' not in environ:
+    return 0, 1, 0, False
+  rank, world = int(environ['RANK']), int(environ['WORLD_SIZE'])
+  return rank, world, int(environ.get('LOCAL_RANK', rank)), True
 
 
 def parse_args(argv=None):
@@ -146,7 +175,45 @@ def parse_args(argv=None):
                   'train.py:437)')
   ap.add_argument('--checkpoint_steps', type=int, default=1000)
   ap.add_argument('--device', type=int, default=0)
+  # synchronous replicas (ffn/training/optimizer.py:58-70)
+  ap.add_argument('--sync_sgd', type=_boolean, nargs='?', const=True,
+                  default=False,
+                  help='every step averages the clipped gradients of '
+                  '--replicas_to_aggregate batches of --batch_size FoVs, all '
+                  'taken under the same variables, and applies them once')
+  ap.add_argument('--replicas_to_aggregate', type=int, default=None,
+                  help='R, the replicas of a step over all ranks of the job; '
+                  'a multiple of the number of ranks')
+  ap.add_argument('--total_replicas', type=int, default=None,
+                  help='accepted only where it equals --replicas_to_aggregate')
+  ap.add_argument('--collective_backend', choices=('nccl', 'gloo'),
+                  default='nccl',
+                  help='torch.distributed backend of a job started by '
+                  'torch.distributed.run: nccl exchanges device arrays, gloo '
+                  'host arrays')
+  ap.add_argument('--ranks_share_gpus', action='store_true',
+                  help='rank k runs on GPU local_rank %% device_count instead '
+                  'of needing a GPU of its own (needs --collective_backend '
+                  'gloo)')
   args = ap.parse_args(argv)
+  world = job_environment()[1]
+  if args.sync_sgd:
+    if args.replicas_to_aggregate is None:
+      ap.error('--sync_sgd needs --replicas_to_aggregate')
+    try:
+      replicas_lib.per_rank(args.replicas_to_aggregate, world)
+    except ValueError as e:
+      ap.error('--replicas_to_aggregate: %s' % e)
+    if (args.total_replicas is not None and
+        args.total_replicas != args.replicas_to_aggregate):
+      ap.error('--total_replicas %d differs from --replicas_to_aggregate %d: '
+               'backup replicas are not mirrored' %
+               (args.total_replicas, args.replicas_to_aggregate))
+    if args.ranks_share_gpus and args.collective_backend == 'nccl':
+      ap.error('--ranks_share_gpus needs --collective_backend gloo: nccl '
+               'cannot run two ranks on one GPU')
+  elif world > 1:
+    ap.error('a job of %d ranks needs --sync_sgd' % world)
   if ((args.image_stddev is None or args.image_mean is None) and
       not args.image_offset_scale_map):
     ap.error('--image_mean, --image_stddev or --image_offset_scale_map need to '
@@ -284,9 +351,174 @@ def write_summary(f, trainer, batches, seconds):
   f.flush()
 
 
+def replica_batches(args, model, volumes, coordinates, seed, replica, ops,
+                    device, result):
+  """The example stream of global replica `replica` of
+  args.replicas_to_aggregate: its shard of the coordinates and its own random
+  streams (replicas.shard, replicas.stream_seeds), so it is the same stream
+  whichever rank hosts it."""
+  seeds = replicas_lib.stream_seeds(seed, replica)
+  transform = augmentation.PermuteAndReflect(
+      args.permutable_axes, args.reflectable_axes,
+      np.random.default_rng(seeds['transform_seed']))
+  sections = None
+  if args.section_augmentation is not None:
+    sections = augmentation.SectionAugmentations(
+        args.section_augmentation,
+        np.random.RandomState(seeds['sections_seed'] % (1 << 32)))
+  geometry = evaluation.Geometry.from_info(model.info, args.fov_policy,
+                                           args.fov_moves, args.batch_size)
+  return examples.BatchExampleIter(
+      model.info, ops, volumes,
+      replicas_lib.shard(coordinates, replica, args.replicas_to_aggregate),
+      fov_policy=args.fov_policy, fov_moves=args.fov_moves,
+      batch_size=args.batch_size, threshold=args.threshold,
+      seed_pad=args.seed_pad, shifts=model.shifts,
+      shuffle_moves=args.shuffle_moves, moves_seed=seeds['moves_seed'],
+      transform=transform, shuffle_seed=seeds['shuffle_seed'],
+      sections=sections, io=examples.torch_io(geometry, args.batch_size, device),
+      result=result)
+
+
+def write_sync_summary(f, trainer, streams, seconds, world):
+  """A summary line of a --sync_sgd run: the loss is the mean over all
+  replicas of the last step; eval/*, moves/* and the counts are those of this
+  rank's replicas (rank 0 writes)."""
+  stats = trainer.last_stats or {}
+  line = {'step': int(trainer.global_step), 'loss': stats.get('loss'),
+          'learning_rate': stats.get('learning_rate'),
+          'clipped': stats.get('clipped'), 'seconds': seconds,
+          'replicas': stats.get('replicas'), 'world': world,
+          'examples_finished': sum(b.examples_finished for b in streams),
+          'epochs': max(b.epochs for b in streams)}
+  line.update(streams[0].result.summaries())
+  if streams[0].sections is not None:
+    for key in streams[0].section_counts:
+      line['augmentation/' + key] = int(sum(b.section_counts[key]
+                                            for b in streams))
+  fresh = evaluation.EvalResult(streams[0].shifts)
+  for b in streams:
+    b.reset_result(fresh)
+  f.write(json.dumps({k: (float(v) if isinstance(v, np.floating) else v)
+                      for k, v in line.items()}, sort_keys=True) + '\n')
+  f.flush()
+
+
+def main_sync(args):
+  """The --sync_sgd run: this process is one rank of the job (the only one
+  outside torch.distributed.run) and hosts R / world replicas."""
+  import torch  # pylint:disable=g-import-not-at-top
+  from ffn_amd.training import trainer as trainer_lib  # pylint:disable=g-import-not-at-top
+  rank, world, local_rank, launched = job_environment()
+  per_rank = replicas_lib.per_rank(args.replicas_to_aggregate, world)
+  device_id = args.device
+  if launched:
+    device_id = (local_rank % max(torch.cuda.device_count(), 1)
+                 if args.ranks_share_gpus else local_rank)
+  group = None
+  if launched:
+    import torch.distributed as dist  # pylint:disable=g-import-not-at-top
+    if args.collective_backend == 'nccl':
+      dist.init_process_group('nccl',
+                              device_id=torch.device('cuda', device_id))
+    else:
+      dist.init_process_group('gloo')
+  trainer, replica_ops = None, []
+  try:
+    if launched:
+      group = replicas_lib.ReplicaGroup(torch.device('cuda', device_id))
+    seed = int(time.time()) if args.seed is None else args.seed
+    if group is not None:
+      seed = group.rank0_value(seed)
+    logging.info('Random seed: %r (rank %d of %d, %d replicas here, GPU %d)',
+                 seed, rank, world, per_rank, device_id)
+    volumes = load_volumes(args)
+    centres, names = coordinate_ops.read_tfrecord(args.train_coords)
+    coordinates = list(zip(centres.tolist(), names))
+    model = import_symbol(args.model_name)(batch_size=args.batch_size,
+                                           **args.model_args)
+    config = optimizer_config(args)
+    resume = newest_checkpoint(args.train_dir)
+    if resume is None:
+      model.init_random(seed=seed % (1 << 32))
+    else:
+      model.load_checkpoint(resume[1])
+    trainer = trainer_lib.ConvStackTrainer(
+        model, config, max_batch=args.batch_size, device_id=device_id,
+        replicas=per_rank, group=group)
+    if resume is not None:
+      trainer.load_state(load_checkpoint(resume[1], resume[2]))
+      logging.info('Resumed from %s at step %d', resume[1],
+                   trainer.global_step)
+    trainer.check_ranks_agree()  # same start, whatever each rank found on disk
+    result, streams = None, []
+    for k in range(per_rank):
+      ops = evaluation.EvaluationOps(device_id)
+      replica_ops.append(ops)
+      batches = replica_batches(
+          args, model, volumes, coordinates, seed,
+          replicas_lib.global_index(rank, k, per_rank), ops, trainer.device,
+          result)
+      result = batches.result
+      streams.append(batches)
+      if batches.skipped:
+        logging.info('replica %d: %d coordinates skipped (patch leaves the '
+                     'volume)', replicas_lib.global_index(rank, k, per_rank),
+                     batches.skipped)
+    chief = rank == 0
+    if chief:
+      os.makedirs(args.train_dir, exist_ok=True)
+    saved = trainer.global_step if resume is not None else None
+
+    def checkpoint():
+      trainer.check_ranks_agree()
+      logging.info('rank %d: ranks agree at step %d', rank,
+                   trainer.global_step)
+      if chief:
+        save_checkpoint(args.train_dir, trainer.state())
+
+    t_begin = t_last = time.time()
+    summ = (open(os.path.join(args.train_dir, 'summaries.jsonl'), 'a')
+            if chief else None)
+    try:
+      while trainer.global_step < args.max_steps:
+        for k, batches in enumerate(streams):
+          seed_io, image, labels, weights = batches.next()
+          _, logits = trainer.contribute(k, seed_io, image, labels, weights)
+          batches.update_seeds(logits)
+        step = trainer.apply_contributions()
+        now = time.time()
+        if chief and now - t_last > args.summary_rate_secs:
+          write_sync_summary(summ, trainer, streams, now - t_begin, world)
+          t_last = now
+        if step % args.checkpoint_steps == 0:
+          checkpoint()
+          saved = step
+      if saved != trainer.global_step:
+        checkpoint()
+      if chief:
+        write_sync_summary(summ, trainer, streams, time.time() - t_begin,
+                           world)
+    finally:
+      if summ is not None:
+        summ.close()
+    logging.info('Done at step %d', trainer.global_step)
+    return trainer.global_step
+  finally:
+    if trainer is not None:
+      trainer.close()
+    for ops in replica_ops:
+      ops.close()
+    if launched:
+      import torch.distributed as dist  # pylint:disable=g-import-not-at-top
+      dist.destroy_process_group()
+
+
 def main(argv=None):
   args = parse_args(argv)
   logging.basicConfig(level=logging.INFO)
+  if args.sync_sgd:
+    return main_sync(args)
   seed = int(time.time()) if args.seed is None else args.seed
   logging.info('Random seed: %r', seed)
   volumes = load_volumes(args)
