@@ -161,13 +161,12 @@ __global__ __launch_bounds__(kConvThreads) void conv32_kernel(ConvArgs a) {
 // Lane -> LDS row is no longer affine in the lane id (row ends / plane ends
 // insert gaps), so each lane carries the LDS offset of its position per tile.
 // ---------------------------------------------------------------------------
-constexpr int kCChunk = 144;
+// (kCChunk = 144: ffn_types.h)
 constexpr int kCTiles = 9;
-// LDS row stride in floats: 32 channels + 8 pad.  With 160-byte rows the
-// ds_read_b128 of 16 consecutive rows is bank-conflict free WITHOUT an XOR
-// swizzle (brute-forced over the b128 lane groups), so the address of every
-// tap is affine: lane base + wave-uniform offset.
-constexpr int kCLdsStride = 40;
+// LDS row stride in floats (kCLdsStride = 40, ffn_types.h): 32 channels + 8 pad.
+// With 160-byte rows the ds_read_b128 of 16 consecutive rows is bank-conflict free
+// WITHOUT an XOR swizzle (brute-forced over the b128 lane groups), so the address of
+// every tap is affine: lane base + wave-uniform offset.
 
 struct ConvCArgs {
   const float* in;

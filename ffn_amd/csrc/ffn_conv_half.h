@@ -44,13 +44,8 @@ namespace ffn {
 // planes of conv32m feed it unchanged;  D: lane l holds position l & 15, out
 // channels 16 h + 4 (l >> 4) .. + 3.
 // ---------------------------------------------------------------------------
-constexpr int kHChunk = 80;
-constexpr int kHRows = 192;  // 80 voxels + 3 row ends + one plane end (XS) + 2 (XS + 1), XS <= 34
-constexpr int kHSeg = 8 * kHRows * 16;            // bytes of a segment slot (24 DMA pieces)
+// (kHChunk = 80, kHRows = 192, kHSeg, kHRingOff, kHUnit, kHLdsBytes: ffn_types.h)
 constexpr int kHPieces = kHSeg / 1024 / 4;        // per wave and segment: 6
-constexpr int kHRingOff = 2 * kHSeg;
-constexpr int kHUnit = 4 * 4096;                  // four taps of weight fragments
-constexpr int kHLdsBytes = kHRingOff + 2 * kHUnit;  // 81,920: two per CU
 static_assert(kHSeg % 4096 == 0 && kHLdsBytes <= 80 * 1024, "two workgroups per CU");
 // (timing-only experiment builds: treat the FoV as its first FFN_H_VCLIP voxels)
 #ifndef FFN_H_VCLIP

@@ -59,10 +59,8 @@ namespace ffn {
 // (No memory operation of the compiler's precedes a DMA it must not wait for:
 // its own vmcnt for such a load would count none of them and drain the queue.)
 // ---------------------------------------------------------------------------
-constexpr int kDChunk = 160;
+// (kDChunk = 160, kDThreads = 256, kDRowB = 144: ffn_types.h)
 constexpr int kDTiles = 5;
-constexpr int kDThreads = 256;
-constexpr int kDRowB = 144;   // epilogue: row stride of the partial sums in LDS
 constexpr int kDTaps = 28;    // 27 + the all-zero tap
 constexpr int kDTapBytes = 2 * 2 * 1024;  // weight fragments of one tap (hi, res)
 
@@ -906,13 +904,8 @@ __global__ __launch_bounds__(kDThreads, WPS) void conv32d_kernel(ConvDArgs a) {
 // tap s waits for W(s+1) (prefetched into registers during tap s); the counts
 // are computed at compile time from that order (m_wait).
 // ---------------------------------------------------------------------------
-constexpr int kMChunk = 128;
-constexpr int kMRows = 240;
+// (kMChunk = 128, kMRows = 240, kMSeg, kMRing, kMRingTaps = 5, kMLdsBytes: ffn_types.h)
 constexpr int kMPieces = 8;                    // DMA pieces per wave and segment
-constexpr int kMSeg = 8 * kMRows * 16;         // bytes of a segment slot
-constexpr int kMRing = 2 * kMSeg;              // LDS offset of the weight ring
-constexpr int kMRingTaps = 5;                  // taps resident in the weight ring
-constexpr int kMLdsBytes = kMRing + kMRingTaps * 4096;  // 81,920: two per CU
 
 // vmcnt for tap S's wait (-1: nothing to wait for): operations issued before it
 // that are NEWER than W(S+1).  D = ring depth: W0 .. W(D-2) are queued in front
@@ -1403,10 +1396,9 @@ __global__ __launch_bounds__(kDThreads, 2) void conv32m_kernel(ConvDArgs a) {
 // voxel is -- runs the SAME tail voxels in 96-voxel workgroups (TNT = 3,
 // conv_variant 7's form) and gets the same bits as a single FoV does.
 // ---------------------------------------------------------------------------
-constexpr int kTRows = 144;   // TNT = 1: rows per dz segment of a tail workgroup
-constexpr int kTPieces = 5;   // its DMA pieces per wave and segment
-constexpr int kT3Rows = 208;  // TNT = 3 (= conv_variant 7's kERows / kEPieces)
-constexpr int kT3Pieces = 7;
+// (kTRows = 144, kT3Rows = 208, the rows per dz segment of a tail workgroup: ffn_types.h)
+constexpr int kTPieces = 5;   // TNT = 1: DMA pieces per wave and segment
+constexpr int kT3Pieces = 7;  // TNT = 3 (= conv_variant 7's kEPieces)
 
 struct ConvTailMap {
   int n;                      // FoVs

@@ -4,6 +4,8 @@
 //   ffn_canvas.hip   everything a canvas does between steps
 //   ffn_options.hip  options, profiler, debug readers (host code only)
 // A helper that more than one of them calls is declared here and defined once.
+// Which conv kernel family runs a stack, and the arithmetic on the FoV that decides it:
+// ffn_stack_plan.h (host only, no HIP; ffn_engine::caps).
 #ifndef FFN_ENGINE_H_
 #define FFN_ENGINE_H_
 
@@ -18,6 +20,7 @@
 
 #include "ffn_internal.h"
 #include "ffn_types.h"
+#include "ffn_stack_plan.h"
 #include "ffn_host_loop.h"
 
 using namespace ffn;
@@ -39,8 +42,6 @@ __attribute__((format(printf, 2, 3))) inline int fail(int code, const char* fmt,
       return fail(FFN_ERR_HIP, "%s failed: %s (%s:%d)", #expr,               \
                   hipGetErrorString(_e), __FILE__, __LINE__);                \
   } while (0)
-
-constexpr int kHeadBlocks = 281;  // head kernel grid.x (4 sweeps of 32 voxels x 281)
 
 struct ffn_engine {
   // Entry points may be called from several host threads (the two canvas groups
@@ -76,12 +77,10 @@ struct ffn_engine {
   int device = 0;
   hipStream_t stream = nullptr;
   Geom g{};   // the FoV as the caller sees it (zyx): gather / paste / faces, I/O
-  Geom gp{};  // the FoV as the split-product kernels (conv_variant >= 6) lay it
-              // out: the same, or with its axes permuted (oa) so that the
-              // SHORTEST axis is the row direction -- rows of 21 instead of 41
-              // voxels put the anisotropic 21 x 41 x 41 FoV inside the row
-              // budget of conv32m / conv32mt
-  bool permuted = false;
+  // what the FoV's geometry fixes for the conv kernels (ffn_stack_plan.h): the layout
+  // of the split-product family (caps.gp), chunk counts, LDS sizes, which families
+  // the FoV admits, the tap schedules
+  ConvCaps caps;
   int depth = 0;
   int max_batch = 0;
   bool weights_set = false;
@@ -91,35 +90,18 @@ struct ffn_engine {
   float* bufX = nullptr;
   uint32_t* validbits = nullptr;
   int32_t* pidx = nullptr;    // dense FoV index -> padded position (variant 2)
-  int nchunks_c = 0, Rc = 0;
   int fuse_head = 1;      // 1x1x1 head fused into the last conv32c launch
   int count_blocks = kHeadBlocks;  // entries per item in `count` for the last step
   int store_policy = 1;  // conv32c epilogue stores: sc1 write-through (-1.4 % per stack)
   long long* d_dbg = nullptr;  // debug clocks of conv32c WG 0 (24 values)
   int dbg_clock = 0;
   int dbg_layer = 3;      // the launch whose clocks are recorded (3 = a conv_a)
-  size_t lds_bytes_c = 0;
-  // conv32d (variant 6): 160-voxel chunks, the 27 taps split over the waves,
-  // split-plane activations, LDS-DMA staging
-  int nchunks_k = 0, Rc_k = 0;
-  bool k_ok = false;             // the chunk + halo fits the LDS slots
   // rawT / rawX / rawS: the three activation allocations
   float* rawT = nullptr;
   float* rawX = nullptr;
   float* rawS = nullptr;
-  bool d_ok = false;
-  // conv32d with 96-voxel chunks, two workgroups per CU (variant 7)
-  bool e_ok = false;
   int batch_chunks = 1;   // option: variant 6 uses the 96-voxel form for n >= 2
-  bool small_now = false; // the stack being queued uses the 96-voxel form
-  // conv32m (variant 8): M split over the waves, weights through an LDS ring
-  bool m_ok = false;
-  bool m_now = false;
-  // conv32mt (variant 9): conv32m for the first n_main <= 256 chunks, 32-voxel
-  // K-split tail workgroups for the rest
-  bool t_ok = false;
-  bool t_now = false;
-  int tail_batched = 0;  // option: steps with >= 2 FoVs take the tail form too
+  int tail_batched = 0;   // option: steps with >= 2 FoVs take conv32mt's tail form too
   // FLOW (ffn_conv_split.h "flagged launches"): 0 off; 1 conv32mt's launches with
   // the flagged hand-off compiled in (still one dependent launch per conv: the
   // words are always there already -- isolates the cost of the sc1 reads and
@@ -145,22 +127,13 @@ struct ffn_engine {
   bool slot_resident[2] = {false, false};
   long long* flow_trace = nullptr; // debug_clock 4: ConvDArgs::flow_trace
   int flow_trace_slots = 0;
-  int n_main = 0, n_tail = 0, n_tail3 = 0;  // tail workgroups of 32 / 96 voxels
-  int tsched_aoff[4 * 8] = {};
-  int t3sched_aoff[4 * 8] = {};
-  int nchunks_m = 0;
-  int nchunks_e = 0;
-  size_t lds_bytes_e = 0;
-  int esched_aoff[4 * 8] = {};
   bool d_weights_ok = true;      // every |weight| x 2^11 inside the fp16 range
   uint16_t* wpackd = nullptr;    // [28][khalf][plane hi, res][64][8] fp16 per layer
   size_t wpackd_layer = 0;       // halves per layer
   // conv32h / conv32hs (variant 10): 80-voxel workgroups on 16x16x32 tiles, two
   // hand-off chains per SIMD for a single FoV; several FoVs run conv32m as under 9
   uint16_t* wpackh = nullptr;    // [28][out half][plane hi, res][64][8] fp16 per layer
-  bool h_ok = false;             // geometry + residency
-  bool h_now = false;            // the stack being queued is conv32h's
-  int n_half = 0;                // 80-voxel chunks of the FoV
+  bool h_ok = false;             // geometry (caps.h_geom_ok) + residency
   // Pacing of the resident stack (ConvStackTab::pace, 10-ns ticks between two convs of a
   // workgroup).  flow_pace: -1 = the beat measured by tune_pace() when the weights were
   // set (conv_variant 9; 0 if no beat beat the free-running stack), 0 = off, > 0 = that
@@ -172,9 +145,6 @@ struct ffn_engine {
   int pace_auto = 0;             // tune_pace()'s beat (0: none)
   float pace_auto_us[2] = {0.f, 0.f};  // us per stack it measured: free-running, at the beat
   int cus = 0;                   // compute units of the device
-  size_t lds_bytes_d = 0;        // 3 slots x 8 planes x Rc_k rows x 16 B
-  int dsched_aoff[4 * 8] = {};
-  int dsched_btap[4 * 8] = {};
   unsigned* range_flag = nullptr;  // device word: tag of the last void run
   // Speculative conv0_a of a single-FoV step's successor (SpecArgs): the launch
   // queued behind the last step's paste, and what a step must match to run on it
@@ -214,8 +184,6 @@ struct ffn_engine {
   bool fp16_ok = true;           // every weight inside the fp16 range
   int conv_variant = 0;       // 0 conv32 (any FoV), 2 conv32c (exact f32), 6 conv32d, 7 = 6
                               // with 96-voxel chunks, 8 conv32m, 9 conv32mt (+ conv32m)
-  int exact_variant = 0;      // the f32 kernel a voided fp16 step is repeated with: 2
-                              // where conv32c takes the FoV, else 0
   float* h_io = nullptr;      // pinned staging of ffn_predict: seed, image, logits
   float* up_image = nullptr;  // dense FoVs uploaded by ffn_predict
   float* up_seed = nullptr;
@@ -290,7 +258,6 @@ struct ffn_engine {
   bool ahead_ev_pending = false;
   double conv_ms = 0.0;
   int64_t conv_launches = 0;
-  size_t lds_bytes = 0;
   std::vector<ffn_canvas*> canvases;  // live canvases created from this engine
   int prof_every = 1;                 // profile 1 of every N run_stack calls
   long stack_calls = 0;

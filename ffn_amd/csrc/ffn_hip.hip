@@ -80,6 +80,24 @@ int flow_voided(ffn_engine* e, bool timed_out) {
               "launch per conv, same arithmetic)");
 }
 
+// Room for one more pair of profiler events: the recorded ones are flushed when fewer
+// than two are left (no allocation: the events were created with the engine).
+int event_pair(ffn_engine* e) {
+  return e->events_used + 2 > (int)e->events.size() ? flush_events(e) : FFN_OK;
+}
+
+// The event pair around ONE conv launch of a sampled stack (profiling mode 1).
+int prof_begin(ffn_engine* e) {
+  if (!e->prof_now) return FFN_OK;
+  if (int rc = event_pair(e)) return rc;
+  HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
+  return FFN_OK;
+}
+int prof_end(ffn_engine* e) {
+  if (e->prof_now) HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
+  return FFN_OK;
+}
+
 template <bool RI, bool RO, bool SK>
 int set_lds_attr(size_t bytes) {
   HIP_TRY(hipFuncSetAttribute(
@@ -97,90 +115,55 @@ inline void split_fp16x2(float x, uint16_t part[2]) {
   std::memcpy(&part[1], &res, 2);
 }
 
+// The forms a split-product conv kernel is launched in: conv_a (KIND 0); conv_b (KIND 1)
+// without and with the residual (SK), each also with the head fused -- which the flagged
+// and the 80-voxel kernels have only with the residual.
+#define FFN_CONV_FORMS4(X) \
+  X(0, false, false); X(1, false, false); X(1, true, false); X(1, true, true)
+#define FFN_CONV_FORMS(X) FFN_CONV_FORMS4(X); X(1, false, true)
+#define FFN_LDS_ATTR(KERNEL, BYTES)                                           \
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL),          \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
+
 int set_lds_attr_d(size_t bytes) {
-#define FFN_D_ATTR(KIND, SK, KSV, HEADV)                                          \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32d_kernel<KIND, SK, KSV, HEADV>),       \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes))
-#define FFN_D_ATTRS(KSV)            \
-  FFN_D_ATTR(0, false, KSV, false); \
-  FFN_D_ATTR(1, false, KSV, false); \
-  FFN_D_ATTR(1, true, KSV, false);  \
-  FFN_D_ATTR(1, false, KSV, true);  \
-  FFN_D_ATTR(1, true, KSV, true)
-  FFN_D_ATTRS(8);
-  FFN_D_ATTRS(9);
-  FFN_D_ATTRS(10);
-#undef FFN_D_ATTRS
-#undef FFN_D_ATTR
+#define FFN_D8(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 8, HEADV>), bytes)
+#define FFN_D9(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 9, HEADV>), bytes)
+#define FFN_D10(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 10, HEADV>), bytes)
+  FFN_CONV_FORMS(FFN_D8);
+  FFN_CONV_FORMS(FFN_D9);
+  FFN_CONV_FORMS(FFN_D10);
+#undef FFN_D8
+#undef FFN_D9
+#undef FFN_D10
   return FFN_OK;
 }
 
-constexpr int kERows = 208, kETiles = 3, kEPieces = 7;
-
 int set_lds_attr_m() {
-#define FFN_M_ATTR(KIND, SK, HEADV)                                               \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32m_kernel<KIND, SK, HEADV>),            \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMLdsBytes))
-  FFN_M_ATTR(0, false, false);
-  FFN_M_ATTR(1, false, false);
-  FFN_M_ATTR(1, true, false);
-  FFN_M_ATTR(1, false, true);
-  FFN_M_ATTR(1, true, true);
-#undef FFN_M_ATTR
-#define FFN_MT_ATTR(KIND, SK, HEADV)                                              \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32mt_kernel<KIND, SK, HEADV, 1>),        \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMLdsBytes));              \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32mt_kernel<KIND, SK, HEADV, 3>),        \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMLdsBytes))
-  FFN_MT_ATTR(0, false, false);
-  FFN_MT_ATTR(1, false, false);
-  FFN_MT_ATTR(1, true, false);
-  FFN_MT_ATTR(1, false, true);
-  FFN_MT_ATTR(1, true, true);
-#undef FFN_MT_ATTR
-#define FFN_MTF_ATTR(KIND, SK, HEADV)                                             \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32mt_kernel<KIND, SK, HEADV, 1, true>),  \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMLdsBytes))
-  FFN_MTF_ATTR(0, false, false);
-  FFN_MTF_ATTR(1, false, false);
-  FFN_MTF_ATTR(1, true, false);
-  FFN_MTF_ATTR(1, true, true);
-#undef FFN_MTF_ATTR
-#define FFN_H_ATTR(KIND, SK, HEADV)                                               \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(&conv32h_kernel<KIND, SK, HEADV>),            \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHLdsBytes))
-  FFN_H_ATTR(0, false, false);
-  FFN_H_ATTR(1, false, false);
-  FFN_H_ATTR(1, true, false);
-  FFN_H_ATTR(1, true, true);
-#undef FFN_H_ATTR
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32hs_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kHLdsBytes));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32ps_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)kMLdsBytes));
+#define FFN_M(KIND, SK, HEADV) FFN_LDS_ATTR((conv32m_kernel<KIND, SK, HEADV>), kMLdsBytes)
+#define FFN_MT(KIND, SK, HEADV)                                          \
+  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 1>), kMLdsBytes);       \
+  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 3>), kMLdsBytes)
+#define FFN_MTF(KIND, SK, HEADV) \
+  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 1, true>), kMLdsBytes)
+#define FFN_H(KIND, SK, HEADV) FFN_LDS_ATTR((conv32h_kernel<KIND, SK, HEADV>), kHLdsBytes)
+  FFN_CONV_FORMS(FFN_M);
+  FFN_CONV_FORMS(FFN_MT);
+  FFN_CONV_FORMS4(FFN_MTF);
+  FFN_CONV_FORMS4(FFN_H);
+#undef FFN_M
+#undef FFN_MT
+#undef FFN_MTF
+#undef FFN_H
+  FFN_LDS_ATTR(conv32hs_kernel, kHLdsBytes);
+  FFN_LDS_ATTR(conv32ps_kernel, kMLdsBytes);
   return FFN_OK;
 }
 
 int set_lds_attr_e(size_t bytes) {
-#define FFN_E_ATTR(KIND, SK, HEADV)                                               \
-  HIP_TRY(hipFuncSetAttribute(                                                    \
-      reinterpret_cast<const void*>(                                              \
-          &conv32d_kernel<KIND, SK, kEPieces, HEADV, kETiles, kERows, 2>),        \
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes))
-  FFN_E_ATTR(0, false, false);
-  FFN_E_ATTR(1, false, false);
-  FFN_E_ATTR(1, true, false);
-  FFN_E_ATTR(1, false, true);
-  FFN_E_ATTR(1, true, true);
-#undef FFN_E_ATTR
+#define FFN_E(KIND, SK, HEADV) \
+  FFN_LDS_ATTR((conv32d_kernel<KIND, SK, kEPieces, HEADV, kETiles, kERows, 2>), bytes)
+  FFN_CONV_FORMS(FFN_E);
+#undef FFN_E
   return FFN_OK;
 }
 
@@ -220,24 +203,23 @@ int launch_conv32(ffn_engine* e, int n, const float* in, float* out,
   a.plane = e->g.plane;
   a.R = e->g.R;
   a.nchunks = e->g.nchunks;
-  const bool prof = e->prof_now;
-  if (prof) {
-    if (e->events_used + 2 > (int)e->events.size()) {
-      int rc = flush_events(e);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  }
+  if (int rc = prof_begin(e)) return rc;
   hipLaunchKernelGGL((conv32_kernel<RI, RO, SK>), dim3(n * e->g.nchunks),
-                     dim3(kConvThreads), e->lds_bytes, e->stream, a);
-  if (prof) HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  return FFN_OK;
+                     dim3(kConvThreads), e->caps.lds_bytes, e->stream, a);
+  return prof_end(e);
 }
 
 struct HeadFusion {
   bool on = false;
   float pad_value = 0.f, move_thr = 0.f;
 };
+HeadFusion head_fusion(bool on, float pad_value, float move_thr) {
+  HeadFusion hf;
+  hf.on = on;
+  hf.pad_value = pad_value;
+  hf.move_thr = move_thr;
+  return hf;
+}
 
 template <bool RI, bool RO, bool SK>
 int launch_conv32c(ffn_engine* e, int n, const float* in, float* out,
@@ -253,12 +235,12 @@ int launch_conv32c(ffn_engine* e, int n, const float* in, float* out,
   a.act_stride = e->g.act_stride;
   a.XS = e->g.XS;
   a.plane = e->g.plane;
-  a.Rc = e->Rc;
-  a.nchunks = e->nchunks_c;
+  a.Rc = e->caps.Rc;
+  a.nchunks = e->caps.nchunks_c;
   a.V = e->g.V;
   a.fx = e->g.fx;
   a.fyfx = e->g.fy * e->g.fx;
-  a.total_slots = n * e->nchunks_c;
+  a.total_slots = n * e->caps.nchunks_c;
   a.slots_per_xcd = (a.total_slots + 7) / 8;
   a.nbytes = (unsigned)((size_t)e->g.nchunks * kChunk * kFeatures * sizeof(float));
   a.store_policy = e->store_policy;
@@ -270,52 +252,33 @@ int launch_conv32c(ffn_engine* e, int n, const float* in, float* out,
   a.head_count = e->count;
   a.pad_value = head.pad_value;
   a.move_thr = head.move_thr;
-  const bool prof = e->prof_now;
-  if (prof) {
-    if (e->events_used + 2 > (int)e->events.size()) {
-      int rc = flush_events(e);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  }
+  if (int rc = prof_begin(e)) return rc;
   const dim3 grid(8 * a.slots_per_xcd), block(kConvThreads);
   a.range_flag = e->range_flag;
   a.range_tag = e->range_tag;
+#define FFN_C_LAUNCH(...)                                                       \
+  hipLaunchKernelGGL((conv32c_kernel<__VA_ARGS__>), grid, block, e->caps.lds_bytes_c, \
+                     e->stream, a)
   if (RI == false && RO == false && SK == true && e->ablate != 0 &&
-      e->Rc == 256) {
+      e->caps.Rc == 256) {
     switch (e->ablate) {  // issue-rate experiments (conv_b instantiation only)
-      case 8:
-        hipLaunchKernelGGL((conv32c_kernel<false, false, true, 8>), grid, block,
-                           e->lds_bytes_c, e->stream, a);
-        break;
-      case 16:
-        hipLaunchKernelGGL((conv32c_kernel<false, false, true, 16>), grid, block,
-                           e->lds_bytes_c, e->stream, a);
-        break;
-      case 24:
-        hipLaunchKernelGGL((conv32c_kernel<false, false, true, 24>), grid, block,
-                           e->lds_bytes_c, e->stream, a);
-        break;
+      case 8: FFN_C_LAUNCH(false, false, true, 8); break;
+      case 16: FFN_C_LAUNCH(false, false, true, 16); break;
+      case 24: FFN_C_LAUNCH(false, false, true, 24); break;
       default:
         return fail(FFN_ERR_ARG, "unsupported ablate mask %d for variant 2",
                     e->ablate);
     }
   } else if (head.on) {
-    if (e->Rc == 256)
-      hipLaunchKernelGGL((conv32c_kernel<RI, RO, SK, 0, 8, true>), grid, block,
-                         e->lds_bytes_c, e->stream, a);
-    else
-      hipLaunchKernelGGL((conv32c_kernel<RI, RO, SK, 0, 9, true>), grid, block,
-                         e->lds_bytes_c, e->stream, a);
-  } else if (e->Rc == 256) {
-    hipLaunchKernelGGL((conv32c_kernel<RI, RO, SK, 0, 8>), grid, block,
-                       e->lds_bytes_c, e->stream, a);
+    if (e->caps.Rc == 256) FFN_C_LAUNCH(RI, RO, SK, 0, 8, true);
+    else FFN_C_LAUNCH(RI, RO, SK, 0, 9, true);
+  } else if (e->caps.Rc == 256) {
+    FFN_C_LAUNCH(RI, RO, SK, 0, 8);
   } else {
-    hipLaunchKernelGGL((conv32c_kernel<RI, RO, SK, 0, 9>), grid, block,
-                       e->lds_bytes_c, e->stream, a);
+    FFN_C_LAUNCH(RI, RO, SK, 0, 9);
   }
-  if (prof) HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  return FFN_OK;
+#undef FFN_C_LAUNCH
+  return prof_end(e);
 }
 
 // The split-plane layout of variant 6 and the f32 layout of the others keep their
@@ -338,9 +301,9 @@ namespace {
 
 // conv32d launch: KIND 0 conv_a (T' = split(relu(conv(X') + b))), KIND 1 conv_b
 // (X = conv(T') + b [+ X]; X' = split(relu(X))), or the fused head
-void conv32d_args(ffn_engine* e, int n, const float* raw_in, float* raw_out, int layer,
-                  const HeadFusion& head, ConvDArgs& a) {
-  const Geom& g = e->gp;
+void conv32d_args(ffn_engine* e, const StackPlan& plan, int n, const float* raw_in,
+                  float* raw_out, int layer, const HeadFusion& head, ConvDArgs& a) {
+  const Geom& g = e->caps.gp;
   const long positions = g.act_stride / kFeatures;
   a.L.in_sp = reinterpret_cast<const char*>(raw_in) + (size_t)g.guard * 16;
   a.L.out_sp = reinterpret_cast<char*>(raw_out) + (size_t)g.guard * 16;
@@ -351,9 +314,12 @@ void conv32d_args(ffn_engine* e, int n, const float* raw_in, float* raw_out, int
   a.sp_plane_bytes = positions * 16;
   a.XS = g.XS;
   a.plane = g.plane;
-  const bool small = e->small_now;  // 96-voxel chunks, 2 workgroups / CU
-  const bool msplit = e->m_now;     // conv32m: 128-voxel chunks, M split
-  const int nchunks = msplit ? e->nchunks_m : small ? e->nchunks_e : e->nchunks_k;
+  // the chunks of a plain launch: conv32m's 128-voxel ones (MT and H bring their own
+  // maps and read conv32m's count), 96-voxel ones, or conv32d's 160-voxel ones
+  const bool small = plan.family == ConvFamily::D96;
+  const int nchunks = small ? e->caps.nchunks_e
+                      : plan.family == ConvFamily::D160 ? e->caps.nchunks_k
+                                                        : e->caps.nchunks_m;
   a.nchunks = nchunks;
   a.V = g.V;
   a.fx = g.fx;
@@ -364,13 +330,13 @@ void conv32d_args(ffn_engine* e, int n, const float* raw_in, float* raw_out, int
   a.magic_nchunks = magic(nchunks);
   a.magic_fyfx = magic(g.fy * g.fx);
   a.magic_fx = magic(g.fx);
-  a.permuted = e->permuted;
+  a.permuted = e->caps.permuted;
   a.ds0 = g.dstr[0];
   a.ds1 = g.dstr[1];
   a.ds2 = g.dstr[2];
   a.sp_bytes = (unsigned)((size_t)g.act_stride * sizeof(float) - (size_t)g.guard * 32);
-  std::memcpy(a.aoff, small ? e->esched_aoff : e->dsched_aoff, sizeof(a.aoff));
-  std::memcpy(a.btap, e->dsched_btap, sizeof(a.btap));
+  std::memcpy(a.aoff, small ? e->caps.esched_aoff : e->caps.dsched_aoff, sizeof(a.aoff));
+  std::memcpy(a.btap, e->caps.dsched_btap, sizeof(a.btap));
   a.L.dbg = (e->dbg_clock && layer == e->dbg_layer) ? e->d_dbg : nullptr;
   a.dbg_wgs = e->dbg_clock == 2 ? 1 : e->dbg_clock == 3 ? 2 : 0;
   a.head_w = e->weights + e->wl_off;
@@ -382,7 +348,7 @@ void conv32d_args(ffn_engine* e, int n, const float* raw_in, float* raw_out, int
   a.range_flag = e->range_flag;
   a.range_tag = e->range_tag;
   a.flow_flags = e->flow_flags;
-  a.flow_n_main = e->n_main;
+  a.flow_n_main = e->caps.n_main;
   a.flow_err = e->flow_err;
   a.flow_halo = g.fy * g.fx + g.fx + 1;
   a.flow_dbg = e->flow_debug;
@@ -395,41 +361,32 @@ void conv32d_args(ffn_engine* e, int n, const float* raw_in, float* raw_out, int
 void tail_map(const ffn_engine* e, int n, ConvTailMap& mp) {
   const bool one = n == 1;
   mp.n = n;
-  mp.n_main = e->n_main;
-  mp.n_tail = one ? e->n_tail : e->n_tail3;
+  mp.n_main = e->caps.n_main;
+  mp.n_tail = one ? e->caps.n_tail : e->caps.n_tail3;
   mp.mains_per_xcd = (mp.n_main + 7) / 8;
   mp.tails_per_xcd = (mp.n_tail + 7) / 8;
-  std::memcpy(mp.taoff, one ? e->tsched_aoff : e->t3sched_aoff, sizeof(mp.taoff));
+  std::memcpy(mp.taoff, one ? e->caps.tsched_aoff : e->caps.t3sched_aoff, sizeof(mp.taoff));
 }
 
 template <int KIND, bool SK>
-int launch_conv32d(ffn_engine* e, int n, const float* raw_in, float* raw_out,
-                   int layer, const HeadFusion& head = HeadFusion()) {
+int launch_conv32d(ffn_engine* e, const StackPlan& plan, int n, const float* raw_in,
+                   float* raw_out, int layer, const HeadFusion& head = HeadFusion()) {
   ConvDArgs a;
-  conv32d_args(e, n, raw_in, raw_out, layer, head, a);
-  const bool small = e->small_now;
-  const bool msplit = e->m_now;
-  const bool prof = e->prof_now;
-  if (prof) {
-    if (e->events_used + 2 > (int)e->events.size()) {
-      int rc = flush_events(e);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  }
+  conv32d_args(e, plan, n, raw_in, raw_out, layer, head, a);
+  if (int rc = prof_begin(e)) return rc;
   const dim3 grid(8 * a.slots_per_xcd), block(kDThreads);
-  const int ks = e->Rc_k / 32;
+  const int ks = e->caps.Rc_k / 32;
 #define FFN_D_LAUNCH(KSV, HEADV)                                                 \
   hipLaunchKernelGGL((conv32d_kernel<KIND, SK, KSV, HEADV>), grid, block,        \
-                     e->lds_bytes_d, e->stream, a)
+                     e->caps.lds_bytes_d, e->stream, a)
 #define FFN_E_LAUNCH(HEADV)                                                      \
   hipLaunchKernelGGL(                                                            \
       (conv32d_kernel<KIND, SK, kEPieces, HEADV, kETiles, kERows, 2>), grid,     \
-      block, e->lds_bytes_e, e->stream, a)
-  if (e->t_now) {
+      block, e->caps.lds_bytes_e, e->stream, a)
+  if (plan.family == ConvFamily::MT) {
     // one FoV: 32-voxel tail workgroups (balance over the CUs); several: the
     // same voxels in 96-voxel ones (cost per voxel) -- the same bits
-    const bool one = n == 1;
+    const bool one = plan.tail_tiles == 1;
     ConvTailMap mp;
     tail_map(e, n, mp);
     const dim3 tgrid(8 * n * (mp.mains_per_xcd + mp.tails_per_xcd));
@@ -456,7 +413,7 @@ int launch_conv32d(ffn_engine* e, int n, const float* raw_in, float* raw_out,
       FFN_MT_LAUNCH(false);
     }
 #undef FFN_MT_LAUNCH
-  } else if (msplit) {
+  } else if (plan.family == ConvFamily::M) {
     if (head.on) {
       if constexpr (KIND == 1)
         hipLaunchKernelGGL((conv32m_kernel<KIND, SK, true>), grid, block,
@@ -465,7 +422,7 @@ int launch_conv32d(ffn_engine* e, int n, const float* raw_in, float* raw_out,
       hipLaunchKernelGGL((conv32m_kernel<KIND, SK, false>), grid, block,
                          kMLdsBytes, e->stream, a);
     }
-  } else if (small) {
+  } else if (plan.family == ConvFamily::D96) {
     if (head.on) {
       if constexpr (KIND == 1) FFN_E_LAUNCH(true);
     } else {
@@ -484,8 +441,7 @@ int launch_conv32d(ffn_engine* e, int n, const float* raw_in, float* raw_out,
   }
 #undef FFN_D_LAUNCH
 #undef FFN_E_LAUNCH
-  if (prof) HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  return FFN_OK;
+  return prof_end(e);
 }
 
 // FoVs described by `si` -> logits (+ count of logits >= move_thr, + seed_raw)
@@ -496,11 +452,11 @@ int launch_conv32d(ffn_engine* e, int n, const float* raw_in, float* raw_out,
 int conv0a_split_args(ffn_engine* e, float pad_value, unsigned tag, const SpecArgs& sp,
                       bool next, Conv0Next& nx) {
   const float* W = e->weights;
-  const Geom& q = e->gp;  // the split-product kernels' layout of the FoV
+  const Geom& q = e->caps.gp;  // the split-product kernels' layout of the FoV
   const int qz = (q.fz + kC0Z - 1) / kC0Z, qy = (q.fy + kC0Y - 1) / kC0Y,
             qx = (q.fx + kC0X - 1) / kC0X;
   nx.pad_value = pad_value;
-  nx.w = W + (e->permuted ? e->w0ap_off : e->w0a_off);
+  nx.w = W + (e->caps.permuted ? e->w0ap_off : e->w0a_off);
   nx.bias = W + e->b0a_off;
   nx.out = e->bufT;
   nx.seed_raw = next ? e->seed_raw_alt : e->seed_raw;
@@ -540,6 +496,32 @@ void launch_conv0a(ffn_engine* e, int n, const StepItems& si, float pad_value,
   }
 }
 
+// What a resident launch of the whole stack adds to a conv's arguments: where the layers'
+// planes, weight fragments (wpack: conv32d's or conv32h's packing) and biases are, its
+// epochs, its beat (auto_pace: the one to run at where the user set none).  An ordinary
+// launch: nothing stamped, nothing ahead.
+void stack_tab(ffn_engine* e, const uint16_t* wpack, int auto_pace, ConvStackTab* tb) {
+  const Geom& g = e->caps.gp;
+  tb->nlayers = 2 * e->depth - 1;
+  tb->dbg_layer = e->dbg_layer;
+  tb->sp_t = reinterpret_cast<const char*>(e->rawT) + (size_t)g.guard * 16;
+  tb->sp_s = reinterpret_cast<char*>(e->rawS) + (size_t)g.guard * 16;
+  tb->wpack0 = reinterpret_cast<const char*>(wpack);
+  tb->wpack_stride = (long)(e->wpackd_layer * sizeof(uint16_t));
+  tb->bias0 = e->weights + e->bias_off[0];
+  tb->bias_stride = e->depth > 1 ? (long)(e->bias_off[1] - e->bias_off[0]) : 0;
+  tb->epoch0 = e->flow_epoch;
+  e->flow_epoch += (unsigned)tb->nlayers;
+  tb->l_begin = 0;
+  tb->l_end = tb->nlayers;
+  tb->pace = e->flow_pace < 0 ? auto_pace : e->flow_pace;
+  tb->pace_tail = 0;
+  tb->pace_spread = e->flow_pace_spread < 0 ? tb->pace : e->flow_pace_spread;
+  tb->stamps = nullptr;
+  tb->ahead_choice = nullptr;
+  tb->trace = 0;
+}
+
 // The 2 depth - 1 convs of ONE FoV as a single resident launch (conv32ps,
 // ffn_conv_resident.h): conv32mt's workgroups keep their voxels through the stack and
 // hand rows to each other through the tile words instead of kernel boundaries.
@@ -547,36 +529,18 @@ void launch_conv0a(ffn_engine* e, int n, const StepItems& si, float pad_value,
 // (hipExtLaunchKernelGGL: the timestamps rocprofv3 reads), not markers queued around it: a
 // marker is a barrier packet with system-scope fences of its own, 2 - 3 us each, which the
 // sampled launch and the step around it would wait behind
-int launch_conv32ps(ffn_engine* e, float pad_value, float move_thr,
+int launch_conv32ps(ffn_engine* e, const StackPlan& plan, float pad_value, float move_thr,
                     const int* ahead_choice = nullptr, hipEvent_t ev0 = nullptr,
                     hipEvent_t ev1 = nullptr) {
-  HeadFusion hf;
-  hf.on = true;
-  hf.pad_value = pad_value;
-  hf.move_thr = move_thr;
   ConvDArgs a;
-  conv32d_args(e, 1, e->rawT, e->rawS, 0, hf, a);
+  conv32d_args(e, plan, 1, e->rawT, e->rawS, 0, head_fusion(true, pad_value, move_thr), a);
   a.L.dbg = e->dbg_clock ? e->d_dbg : nullptr;
   ConvTailMap mp;
   tail_map(e, 1, mp);
-  const Geom& g = e->gp;
   ConvStackTab tb;
-  tb.nlayers = 2 * e->depth - 1;
-  tb.dbg_layer = e->dbg_layer;
-  tb.sp_t = reinterpret_cast<const char*>(e->rawT) + (size_t)g.guard * 16;
-  tb.sp_s = reinterpret_cast<char*>(e->rawS) + (size_t)g.guard * 16;
-  tb.wpack0 = reinterpret_cast<const char*>(e->wpackd);
-  tb.wpack_stride = (long)(e->wpackd_layer * sizeof(uint16_t));
-  tb.bias0 = e->weights + e->bias_off[0];
-  tb.bias_stride = e->depth > 1 ? (long)(e->bias_off[1] - e->bias_off[0]) : 0;
-  tb.epoch0 = e->flow_epoch;
-  tb.pace = e->flow_pace < 0 ? e->pace_auto : e->flow_pace;
+  stack_tab(e, e->wpackd, e->pace_auto, &tb);
   tb.pace_tail = e->flow_pace_tail;
-  tb.pace_spread = e->flow_pace_spread < 0 ? tb.pace : e->flow_pace_spread;
-  e->flow_epoch += (unsigned)tb.nlayers;
   const dim3 grid(8 * (mp.mains_per_xcd + mp.tails_per_xcd)), block(kDThreads);
-  tb.l_begin = 0;
-  tb.l_end = tb.nlayers;
   tb.stamps = e->d_stamps;
   tb.ahead_choice = ahead_choice;
   // (2: the stack in front of the traced step, queued ahead one call earlier: its end only)
@@ -602,19 +566,19 @@ int launch_conv32ps(ffn_engine* e, float pad_value, float move_thr,
 // The same stack on 64-voxel workgroups, two per CU (conv32hs, ffn_conv_half.h).
 void half_map(const ffn_engine* e, ConvHalfMap& mp) {
   // (the dispatcher hands an XCD's first blocks to its empty CUs: cus / 8 first slots)
-  mp.n_chunks = e->n_half;
+  mp.n_chunks = e->caps.n_half;
   mp.per_first = std::max(1, e->cus / 8);
-  mp.n_first = std::min(e->n_half, 8 * mp.per_first);
-  mp.per_second = (e->n_half - mp.n_first + 7) / 8;
+  mp.n_first = std::min(e->caps.n_half, 8 * mp.per_first);
+  mp.per_second = (e->caps.n_half - mp.n_first + 7) / 8;
 }
 
 // one conv of the 80-voxel family as its own launch: what a resident step that came
 // back void is repeated with (the same bits), and flow = 0
 template <int KIND, bool SK>
-int launch_conv32h(ffn_engine* e, const float* raw_in, float* raw_out, int layer,
-                   const HeadFusion& head = HeadFusion()) {
+int launch_conv32h(ffn_engine* e, const StackPlan& plan, const float* raw_in, float* raw_out,
+                   int layer, const HeadFusion& head = HeadFusion()) {
   ConvDArgs a;
-  conv32d_args(e, 1, raw_in, raw_out, layer, head, a);
+  conv32d_args(e, plan, 1, raw_in, raw_out, layer, head, a);
   a.L.wpack = reinterpret_cast<const char*>(e->wpackh + (size_t)layer * e->wpackd_layer);
   a.flow_n_main = -1;
   ConvHalfMap mp;
@@ -631,39 +595,36 @@ int launch_conv32h(ffn_engine* e, const float* raw_in, float* raw_out, int layer
   return FFN_OK;
 }
 
-int launch_conv32hs(ffn_engine* e, float pad_value, float move_thr) {
-  HeadFusion hf;
-  hf.on = true;
-  hf.pad_value = pad_value;
-  hf.move_thr = move_thr;
+int launch_conv32hs(ffn_engine* e, const StackPlan& plan, float pad_value, float move_thr) {
   ConvDArgs a;
-  conv32d_args(e, 1, e->rawT, e->rawS, 0, hf, a);
+  conv32d_args(e, plan, 1, e->rawT, e->rawS, 0, head_fusion(true, pad_value, move_thr), a);
   a.flow_n_main = -1;
   ConvHalfMap mp;
   half_map(e, mp);
-  const Geom& g = e->gp;
   ConvStackTab tb;
-  tb.nlayers = 2 * e->depth - 1;
-  tb.dbg_layer = e->dbg_layer;
-  tb.sp_t = reinterpret_cast<const char*>(e->rawT) + (size_t)g.guard * 16;
-  tb.sp_s = reinterpret_cast<char*>(e->rawS) + (size_t)g.guard * 16;
-  tb.wpack0 = reinterpret_cast<const char*>(e->wpackh);
-  tb.wpack_stride = (long)(e->wpackd_layer * sizeof(uint16_t));
-  tb.bias0 = e->weights + e->bias_off[0];
-  tb.bias_stride = e->depth > 1 ? (long)(e->bias_off[1] - e->bias_off[0]) : 0;
-  tb.epoch0 = e->flow_epoch;
-  e->flow_epoch += (unsigned)tb.nlayers;
-  tb.l_begin = 0;
-  tb.l_end = tb.nlayers;
-  tb.pace = e->flow_pace < 0 ? 0 : e->flow_pace;  // (no measured beat for this family)
-  tb.pace_tail = 0;
-  tb.pace_spread = e->flow_pace_spread < 0 ? tb.pace : e->flow_pace_spread;
-  tb.stamps = nullptr;
-  tb.ahead_choice = nullptr;
-  tb.trace = 0;
+  stack_tab(e, e->wpackh, 0, &tb);  // (no measured beat for this family)
   const dim3 grid(8 * (mp.per_first + mp.per_second)), block(kDThreads);
   hipLaunchKernelGGL(conv32hs_kernel, grid, block, kHLdsBytes, e->stream, a, mp, tb);
   return FFN_OK;
+}
+
+// The plan of a stack of n FoVs as the engine's options stand (flow_skip: the engine's,
+// or 0 for "once no repeat is pending").
+StackPlan plan_for(const ffn_engine* e, int n, int flow_skip) {
+  return plan_stack(e->caps, e->conv_variant, e->flow, flow_skip, e->tail_batched,
+                    e->batch_chunks, n);
+}
+
+// The chain of launches of a stack, one per conv: conv0_b, then per residual module
+// conv_a (layer 2 i - 1) and conv_b (layer 2 i; last: the one that may take the head).
+template <class First, class A, class B>
+int walk_stack(int depth, First first, A conv_a, B conv_b) {
+  int rc = first();
+  for (int i = 1; i < depth && !rc; ++i) {
+    rc = conv_a(2 * i - 1);
+    if (!rc) rc = conv_b(2 * i, i == depth - 1);
+  }
+  return rc;
 }
 
 // conv0a_done: the step's conv0_a has been queued already (a speculative launch
@@ -690,23 +651,22 @@ int run_stack(ffn_engine* e, int n, const StepItems& si, float pad_value,
   e->prof_now = e->prof_mode == 1 && sampled;
   const bool prof_chain = e->prof_mode == 2 && sampled;
   if (!conv0a_done) launch_conv0a(e, n, si, pad_value, e->range_tag, SpecArgs());
-  int rc;
-  const float* head_in;
   bool head_fused = false;
   e->ahead_ev_pending = false;
+  const StackPlan plan = plan_for(e, n, e->flow_skip);
+  if ((plan.family == ConvFamily::MT || plan.family == ConvFamily::H) && n == 1 &&
+      e->flow == 2 && e->flow_skip > 0)
+    e->flow_skip -= 1;  // the repeat of a voided resident step: per-layer launches
   // a sampled stack that runs as ONE resident launch is timed by that dispatch's own
-  // start / end (launch_conv32ps); a chain of launches by markers around it
-  const bool one_launch = e->conv_variant == 9 && n == 1 && e->flow == 2 &&
-                          e->flow_skip == 0 && e->tail_batched == 0;
+  // start / end (launch_conv32ps); a chain of launches by markers around it (and so is
+  // conv32hs, and the resident launch of an engine with tail_batched set)
+  const bool one_launch = resident_mt(plan) && e->tail_batched == 0;
   hipEvent_t k_ev0 = nullptr, k_ev1 = nullptr;
   if (prof_chain && ahead) {
     if (one_launch) k_ev0 = e->ahead_ev[0], k_ev1 = e->ahead_ev[1];
     else HIP_TRY(hipEventRecord(e->ahead_ev[0], e->stream));
   } else if (prof_chain) {
-    if (e->events_used + 2 > (int)e->events.size()) {
-      rc = flush_events(e);
-      if (rc) return rc;
-    }
+    if (int rc = event_pair(e)) return rc;
     e->chain_launches_pending.push_back(2 * e->depth - 1);
     if (one_launch) {
       k_ev0 = e->events[e->events_used], k_ev1 = e->events[e->events_used + 1];
@@ -715,120 +675,72 @@ int run_stack(ffn_engine* e, int n, const StepItems& si, float pad_value,
       HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
     }
   }
-  // conv32d: one workgroup per CU (160-voxel chunks) for a single FoV; with
-  // several FoVs in flight the 96-voxel form (two workgroups per CU, the same
-  // arithmetic bit for bit) overlaps one workgroup's MFMAs with the other's
-  // staging and epilogue
-  e->small_now = e->conv_variant == 7 ||
-                 (e->conv_variant == 6 && e->batch_chunks == 1 && n >= 2 && e->e_ok);
-  e->m_now = e->conv_variant >= 8 ||
-             (e->conv_variant == 6 && e->batch_chunks == 2 && n >= 2 && e->m_ok);
-  // variant 9: a single FoV runs conv32mt (balance over the CUs: +14 %); steps
-  // with several FoVs run plain conv32m (cost per voxel: the K-split tail costs
-  // 5-10 % there) unless tail_batched asks for the single-FoV bits
-  e->t_now = e->conv_variant == 9 && (n == 1 || e->tail_batched != 0);
-  // variant 10: a single FoV on 80-voxel workgroups (conv32hs / conv32h); steps with
-  // several FoVs run plain conv32m, as under 9
-  e->h_now = e->conv_variant == 10 && n == 1;
-  if (e->conv_variant >= 6) {
-    if (e->depth == 1)
-      return fail(FFN_ERR_ARG, "conv_variant 6 needs depth >= 2 (fused head)");
-    // T' -> (X, X') -> T' -> ... ; the head is always fused into the last conv_b
-    auto chain = [&]() -> int {
-      if (e->h_now) {
-        if (e->flow == 2 && e->flow_skip > 0) {
-          e->flow_skip -= 1;  // the repeat of a voided resident step
-        } else if (e->flow == 2) {
-          e->last_stack_resident = true;
-          return launch_conv32hs(e, pad_value, move_thr);
-        }
-        int r = launch_conv32h<1, false>(e, e->rawT, e->rawS, 0);
-        for (int i = 1; i < e->depth && !r; ++i) {
-          r = launch_conv32h<0, false>(e, e->rawS, e->rawT, 2 * i - 1);
-          if (r) break;
-          HeadFusion hf;
-          hf.on = i == e->depth - 1;
-          hf.pad_value = pad_value;
-          hf.move_thr = move_thr;
-          r = launch_conv32h<1, true>(e, e->rawT, e->rawS, 2 * i, hf);
-        }
-        return r;
-      }
-      if (e->t_now && n == 1 && e->flow == 2) {
-        if (e->flow_skip > 0) {
-          e->flow_skip -= 1;  // the repeat of a voided resident step
-        } else {
-          e->last_stack_resident = true;
-          return launch_conv32ps(e, pad_value, move_thr, ahead ? e->d_spec_choice : nullptr,
-                                 k_ev0, k_ev1);
-        }
-      }
-      if (ahead) return fail(FFN_ERR_STATE, "stack_ahead without the resident launch");
-      int r = launch_conv32d<1, false>(e, n, e->rawT, e->rawS, 0);
-      for (int i = 1; i < e->depth && !r; ++i) {
-        r = launch_conv32d<0, false>(e, n, e->rawS, e->rawT, 2 * i - 1);
-        if (r) break;
-        HeadFusion hf;
-        hf.on = i == e->depth - 1;
-        hf.pad_value = pad_value;
-        hf.move_thr = move_thr;
-        r = launch_conv32d<1, true>(e, n, e->rawT, e->rawS, 2 * i, hf);
-      }
-      return r;
-    };
-    rc = chain();
-    if (rc) return rc;
+  int rc;
+  if (e->conv_variant >= 6 && e->depth == 1)
+    return fail(FFN_ERR_ARG, "conv_variant 6 needs depth >= 2 (fused head)");
+  if (ahead && !resident_mt(plan))
+    return fail(FFN_ERR_STATE, "stack_ahead without the resident launch");
+  // the split-product families: T' -> (X, X') -> T' -> ... ; the head is always fused
+  // into the last conv_b
+  const auto head = [&](bool on) { return head_fusion(on, pad_value, move_thr); };
+  e->last_stack_resident = plan.resident;
+  if (plan.resident) {
+    rc = plan.family == ConvFamily::H
+             ? launch_conv32hs(e, plan, pad_value, move_thr)
+             : launch_conv32ps(e, plan, pad_value, move_thr,
+                               ahead ? e->d_spec_choice : nullptr, k_ev0, k_ev1);
     head_fused = true;
-    head_in = e->bufX;
-  } else if (e->conv_variant == 0) {
-    rc = launch_conv32<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0);
-    if (rc) return rc;
-    for (int i = 1; i < e->depth; ++i) {
-      rc = launch_conv32<true, true, false>(e, n, e->bufX, e->bufT, nullptr,
-                                            2 * i - 1);
-      if (rc) return rc;
-      rc = launch_conv32<false, false, true>(e, n, e->bufT, e->bufX, e->bufX,
-                                             2 * i);
-      if (rc) return rc;
-    }
-    head_in = e->bufX;
+  } else if (plan.family == ConvFamily::H) {
+    rc = walk_stack(
+        e->depth, [&] { return launch_conv32h<1, false>(e, plan, e->rawT, e->rawS, 0); },
+        [&](int l) { return launch_conv32h<0, false>(e, plan, e->rawS, e->rawT, l); },
+        [&](int l, bool last) {
+          return launch_conv32h<1, true>(e, plan, e->rawT, e->rawS, l, head(last));
+        });
+    head_fused = true;
+  } else if (e->conv_variant >= 6) {
+    rc = walk_stack(
+        e->depth, [&] { return launch_conv32d<1, false>(e, plan, n, e->rawT, e->rawS, 0); },
+        [&](int l) { return launch_conv32d<0, false>(e, plan, n, e->rawS, e->rawT, l); },
+        [&](int l, bool last) {
+          return launch_conv32d<1, true>(e, plan, n, e->rawT, e->rawS, l, head(last));
+        });
+    head_fused = true;
+  } else if (plan.family == ConvFamily::Conv32) {
+    rc = walk_stack(
+        e->depth,
+        [&] { return launch_conv32<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0); },
+        [&](int l) { return launch_conv32<true, true, false>(e, n, e->bufX, e->bufT, nullptr, l); },
+        [&](int l, bool) {
+          return launch_conv32<false, false, true>(e, n, e->bufT, e->bufX, e->bufX, l);
+        });
   } else {
     // conv_variant 2: T is post-ReLU (conv0_a / conv_a apply it), X is the raw
     // residual stream
-    rc = launch_conv32c<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0);
-    if (rc) return rc;
-    for (int i = 1; i < e->depth; ++i) {
-      rc = launch_conv32c<true, true, false>(e, n, e->bufX, e->bufT, nullptr,
-                                             2 * i - 1);
-      if (rc) return rc;
-      HeadFusion hf;
-      hf.on = e->fuse_head && i == e->depth - 1 && e->ablate == 0;
-      hf.pad_value = pad_value;
-      hf.move_thr = move_thr;
-      rc = launch_conv32c<false, false, true>(e, n, e->bufT, e->bufX, e->bufX,
-                                              2 * i, hf);
-      if (rc) return rc;
-      head_fused = hf.on;
-    }
-    head_in = e->bufX;
+    rc = walk_stack(
+        e->depth,
+        [&] { return launch_conv32c<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0); },
+        [&](int l) {
+          return launch_conv32c<true, true, false>(e, n, e->bufX, e->bufT, nullptr, l);
+        },
+        [&](int l, bool last) {
+          head_fused = e->fuse_head && last && e->ablate == 0;
+          return launch_conv32c<false, false, true>(e, n, e->bufT, e->bufX, e->bufX, l,
+                                                    head(head_fused));
+        });
   }
+  if (rc) return rc;
   if (prof_chain && ahead) {
     if (!k_ev0) HIP_TRY(hipEventRecord(e->ahead_ev[1], e->stream));
     e->ahead_ev_pending = true;
   } else if (prof_chain && !k_ev0) {
     HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
   }
-  if (head_fused) {
-    e->count_blocks = e->h_now ? e->n_half
-                      : e->t_now ? e->n_main + (n == 1 ? e->n_tail : e->n_tail3)
-                      : e->m_now ? e->nchunks_m : e->small_now ? e->nchunks_e
-                      : e->conv_variant >= 6 ? e->nchunks_k : e->nchunks_c;
-  } else {
-    e->count_blocks = kHeadBlocks;
+  e->count_blocks = head_fused ? plan.chunks : kHeadBlocks;
+  if (!head_fused)
     hipLaunchKernelGGL(head_kernel, dim3(kHeadBlocks, n), dim3(256), 0, e->stream,
-                       head_in, e->seed_raw, pad_value, W + e->wl_off, move_thr,
+                       e->bufX, e->seed_raw, pad_value, W + e->wl_off, move_thr,
                        e->logits, e->count, g);
-  }
   HIP_TRY(hipGetLastError());
   return FFN_OK;
 }
@@ -841,10 +753,7 @@ int dense_items(ffn_engine* e, int n, StepItems* si) {
     StepItem& it = e->h_items[k];
     std::memset(&it, 0, sizeof(it));
     it.image = e->up_image + (size_t)k * g.V;
-    it.image_u8 = nullptr;
-    it.image_lut = nullptr;
     it.seed = e->up_seed + (size_t)k * g.V;
-    it.seg = nullptr;
     it.cz = g.fz;
     it.cy = g.fy;
     it.cx = g.fx;
@@ -861,6 +770,47 @@ int dense_items(ffn_engine* e, int n, StepItems* si) {
   return FFN_OK;
 }
 
+
+// what the stateless calls check before they touch the device
+int check_batch(const ffn_engine* e, int n) {
+  if (n < 1 || n > e->max_batch)
+    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
+  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  return FFN_OK;
+}
+
+// The stack on the n uploaded FoVs, until a run counts.  A void run is repeated: after a
+// time-out of the resident launch with per-layer launches of the same kernels (same
+// bits), after a range error -- also one that only shows in that repeat -- with the
+// exact-f32 kernel.  At most two repeats.  after_run: queued behind every run (the copy
+// of its logits, where they leave the engine run by run); who: the caller, for the error.
+template <class AfterRun>
+int predict_uploaded(ffn_engine* e, int n, const char* who, AfterRun after_run) {
+  StepItems si;
+  int rc = dense_items(e, n, &si);
+  if (rc) return rc;
+  for (int attempt = 0;; ++attempt) {
+    // NaNs in a caller-provided seed stay NaN (the reference would feed them to TF).
+    rc = run_stack(e, n, si, std::nanf(""), INFINITY);
+    if (!rc) rc = after_run();
+    if (rc) return rc;
+    unsigned flag[2] = {0, 0};
+    if (e->conv_variant >= 6)
+      HIP_TRY(hipMemcpyAsync(flag, e->range_flag, sizeof(flag), hipMemcpyDeviceToHost,
+                             e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const bool is_void = e->conv_variant >= 6 && flag[0] == e->range_tag;
+    if (!is_void) {
+      if (e->last_stack_resident) e->flow_strikes = 0;
+      return FFN_OK;
+    }
+    if (attempt == 2) return fail(FFN_ERR_HIP, "%s: the step stayed void", who);
+    if (flow_voided(e, flag[1] == e->range_tag) == 0) {
+      rc = switch_variant(e, e->caps.exact_variant);
+      if (rc) return rc;
+    }
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -900,84 +850,17 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
   e->depth = depth;
   e->max_batch = max_batch;
   Geom& g = e->g;
-  g.fz = fov_zyx[0];
-  g.fy = fov_zyx[1];
-  g.fx = fov_zyx[2];
-  g.dz = deltas_zyx[0];
-  g.dy = deltas_zyx[1];
-  g.dx = deltas_zyx[2];
-  g.XS = g.fx + 1;
-  g.plane = (g.fy + 1) * g.XS;
-  g.npos = g.fz * g.plane;
-  g.guard = g.plane + g.XS + 1;
-  g.nchunks = (g.npos + kChunk - 1) / kChunk;
-  g.V = g.fz * g.fy * g.fx;
-  g.R = kChunk + 2 * (g.XS + 1);
-  g.oa[0] = 0, g.oa[1] = 1, g.oa[2] = 2;
-  g.dstr[0] = g.fy * g.fx, g.dstr[1] = g.fx, g.dstr[2] = 1;
-  g.crop = 0;
-  g.c0[0] = g.c0[1] = g.c0[2] = 0;
-  g.c1[0] = g.fz, g.c1[1] = g.fy, g.c1[2] = g.fx;
-  g.Vp = g.V;
-  // the geometry with its axes permuted: internal axis a = original axis oa[a]
-  auto permute = [&](const int oa[3]) {
-    const int f[3] = {g.fz, g.fy, g.fx}, d[3] = {g.dz, g.dy, g.dx};
-    const int ds[3] = {g.fy * g.fx, g.fx, 1};
-    Geom q = g;
-    q.fz = f[oa[0]], q.fy = f[oa[1]], q.fx = f[oa[2]];
-    q.dz = d[oa[0]], q.dy = d[oa[1]], q.dx = d[oa[2]];
-    q.XS = q.fx + 1;
-    q.plane = (q.fy + 1) * q.XS;
-    q.npos = q.fz * q.plane;
-    q.guard = q.plane + q.XS + 1;
-    q.nchunks = (q.npos + kChunk - 1) / kChunk;
-    q.R = kChunk + 2 * (q.XS + 1);
-    for (int a = 0; a < 3; ++a) q.oa[a] = oa[a], q.dstr[a] = ds[oa[a]];
-    return q;
-  };
-  // largest padded span of `count` chunks of `chunk` dense voxels from `start`
-  auto chunk_span = [](const Geom& q, int start, int chunk, int count) {
-    auto pad = [&](int v) {
-      const int x = v % q.fx, y = (v / q.fx) % q.fy, z = v / (q.fx * q.fy);
-      return z * q.plane + y * q.XS + x;
-    };
-    int span = 0;
-    for (int c = 0; c < count; ++c) {
-      const int lo = start + c * chunk, hi = std::min(q.V, lo + chunk) - 1;
-      if (lo <= hi) span = std::max(span, pad(hi) - pad(lo) + 1);
-    }
-    return span;
-  };
-  auto m_fits = [&](const Geom& q) {  // conv32m's 128-voxel chunks in kMRows rows
-    return chunk_span(q, 0, kMChunk, (q.V + kMChunk - 1) / kMChunk) +
-               2 * (q.XS + 1) <= kMRows;
-  };
-  e->gp = g;
-  if (!m_fits(g)) {
-    // shortest axis last (= the row direction), the other two in their order
-    static const int kPerms[5][3] = {{0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1},
-                                     {2, 1, 0}};
-    int best = -1;
-    for (int k = 0; k < 5; ++k) {
-      const Geom q = permute(kPerms[k]);
-      if (m_fits(q) && (best < 0 || q.fx < permute(kPerms[best]).fx)) best = k;
-    }
-    if (best >= 0) {
-      e->gp = permute(kPerms[best]);
-      e->permuted = true;
-    }
-  }
-  const long positions = std::max(
-      (long)g.guard + (long)g.nchunks * kChunk + g.guard + 320,
-      (long)e->gp.guard + (long)e->gp.nchunks * kChunk + e->gp.guard + 320);
-  g.act_stride = positions * kFeatures;
-  e->gp.act_stride = g.act_stride;
-  e->lds_bytes = (size_t)3 * g.R * kFeatures * sizeof(float);
-  if (e->lds_bytes > 160 * 1024) {
+  g = fov_geom(fov_zyx, deltas_zyx);
+  // everything the geometry fixes for the conv kernels, before the first allocation
+  e->caps = conv_caps(g, depth);
+  const ConvCaps& caps = e->caps;
+  g.act_stride = caps.act_stride;
+  if (caps.lds_bytes > 160 * 1024) {
+    const size_t bytes = caps.lds_bytes;
     delete e;
-    return fail(FFN_ERR_ARG, "fov too wide for the LDS-staged conv (%zu B)",
-                e->lds_bytes);
+    return fail(FFN_ERR_ARG, "fov too wide for the LDS-staged conv (%zu B)", bytes);
   }
+  e->conv_variant = caps.default_variant;
 
 #define E_TRY(expr)                                                          \
   do {                                                                       \
@@ -1042,148 +925,48 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
                     hipMemcpyHostToDevice));
   }
 
-  // dense -> padded position table and LDS extent of the compact variant
+  // dense -> padded position table of the compact variant
   {
-    e->nchunks_c = (g.V + kCChunk - 1) / kCChunk;
-    e->nchunks_k = (g.V + kDChunk - 1) / kDChunk;
-    std::vector<int32_t> pidx(std::max((size_t)e->nchunks_c * kCChunk,
-                                       (size_t)e->nchunks_k * kDChunk));
+    std::vector<int32_t> pidx(std::max((size_t)caps.nchunks_c * kCChunk,
+                                       (size_t)caps.nchunks_k * kDChunk));
     for (size_t v = 0; v < pidx.size(); ++v) {
       const int vv = (int)std::min<size_t>(v, (size_t)g.V - 1);
       const int x = vv % g.fx, y = (vv / g.fx) % g.fy, z = vv / (g.fx * g.fy);
       pidx[v] = z * g.plane + y * g.XS + x;
-    }
-    int span = 0;
-    for (int c = 0; c < e->nchunks_c; ++c)
-      span = std::max(span, pidx[(size_t)c * kCChunk + kCChunk - 1] -
-                                pidx[(size_t)c * kCChunk] + 1);
-    e->Rc = ((span + 2 * (g.XS + 1)) + 31) / 32 * 32;
-    if (e->Rc < 256) e->Rc = 256;  // the kernel stages 8 or 9 x 256 float4
-    e->lds_bytes_c = (size_t)2 * e->Rc * kCLdsStride * sizeof(float);
-    {
-      // everything from here on is the split-product family: laid out as gp
-      const Geom& q = e->gp;
-      const int span_k = chunk_span(q, 0, kDChunk, e->nchunks_k);
-      e->Rc_k = ((span_k + 2 * (q.XS + 1)) + 31) / 32 * 32;
-      if (e->Rc_k < 256) e->Rc_k = 256;
-      e->k_ok = e->Rc_k <= 320 && e->nchunks_k >= 2;  // (magic divisions: d >= 2)
-      // tap schedule of the four waves (see conv32d_body): two dz = -1 taps
-      // each, then two taps of dz <= 0, then the rest; 7 / 7 / 7 / 6 taps
-      static const int kSched[4][7] = {{0, 1, 8, 9, 16, 18, 19},
-                                       {2, 3, 10, 11, 17, 20, 21},
-                                       {4, 5, 12, 13, 22, 23, 24},
-                                       {6, 7, 14, 15, 25, 26, -1}};
-      // in the plane-major LDS image (8 planes x Rc_k
-      // rows x 16 B per segment); wave 3's seventh tap is the all-zero tap 27
-      e->lds_bytes_d = std::max((size_t)3 * 128 * e->Rc_k,
-                                (size_t)4 * kDChunk * kDRowB + 64);
-      for (int w = 0; w < 4; ++w)
-        for (int j = 0; j < 7; ++j) {
-          int s = kSched[w][j];
-          const bool dummy = s < 0;
-          if (dummy) s = kSched[w][j - 1];
-          const int kz = s / 9, ky = (s / 3) % 3, kx = s % 3;
-          e->dsched_aoff[w * 8 + j] =
-              kz * 128 * e->Rc_k + ((ky - 1) * q.XS + (kx - 1)) * 16;
-          e->dsched_btap[w * 8 + j] = dummy ? 27 : s;
-        }
-      e->d_ok = e->k_ok && e->lds_bytes_d <= 160 * 1024 && depth >= 2;
-      // variant 7: 96-voxel chunks in kERows rows, three slots in 80 KB
-      {
-        const int ce = 32 * kETiles;
-        e->nchunks_e = (q.V + ce - 1) / ce;
-        const int span_e = chunk_span(q, 0, ce, e->nchunks_e);
-        e->lds_bytes_e = std::max((size_t)3 * 128 * kERows,
-                                  (size_t)4 * ce * kDRowB + 64);
-        e->e_ok = e->d_ok && span_e + 2 * (q.XS + 1) <= kERows &&
-                  e->nchunks_e >= 2 && e->lds_bytes_e <= 80 * 1024;
-        // variant 8: 128-voxel chunks in kMRows rows
-        e->nchunks_m = (q.V + kMChunk - 1) / kMChunk;
-        const int span_m = chunk_span(q, 0, kMChunk, e->nchunks_m);
-        e->m_ok = e->d_ok && span_m + 2 * (q.XS + 1) <= kMRows && e->nchunks_m >= 2;
-        // variant 9: the chunks past the 256th become 32-voxel tail workgroups,
-        // as long as all of one FoV's workgroups find a slot at once (two per CU)
-        if (e->m_ok && e->nchunks_m > 256) {
-          e->n_main = 256;
-          e->n_tail = (q.V - 256 * kMChunk + 31) / 32;
-          e->n_tail3 = (q.V - 256 * kMChunk + 95) / 96;
-          const int span_t = chunk_span(q, 256 * kMChunk, 32, e->n_tail);
-          const int span_t3 = chunk_span(q, 256 * kMChunk, 96, e->n_tail3);
-          static_assert((size_t)3 * 128 * kTRows <= kMLdsBytes &&
-                            (size_t)4 * 32 * kDRowB + 64 <= kMLdsBytes &&
-                            (size_t)3 * 128 * kT3Rows <= kMLdsBytes &&
-                            (size_t)4 * 96 * kDRowB + 64 <= kMLdsBytes,
-                        "a tail workgroup fits conv32m's LDS");
-          e->t_ok = span_t + 2 * (q.XS + 1) <= kTRows &&
-                    span_t3 + 2 * (q.XS + 1) <= kT3Rows && e->n_tail <= 256;
-          for (int w = 0; w < 4; ++w)
-            for (int j = 0; j < 7; ++j) {
-              int s = kSched[w][j];
-              if (s < 0) s = kSched[w][j - 1];
-              const int kz = s / 9, ky = (s / 3) % 3, kx = s % 3;
-              e->tsched_aoff[w * 8 + j] =
-                  kz * 128 * kTRows + ((ky - 1) * q.XS + (kx - 1)) * 16;
-              e->t3sched_aoff[w * 8 + j] =
-                  kz * 128 * kT3Rows + ((ky - 1) * q.XS + (kx - 1)) * 16;
-            }
-        }
-        for (int w = 0; w < 4; ++w)
-          for (int j = 0; j < 7; ++j) {
-            int s = kSched[w][j];
-            if (s < 0) s = kSched[w][j - 1];
-            const int kz = s / 9, ky = (s / 3) % 3, kx = s % 3;
-            e->esched_aoff[w * 8 + j] =
-                kz * 128 * kERows + ((ky - 1) * q.XS + (kx - 1)) * 16;
-          }
-      }
     }
     E_TRY(hipMalloc(&e->d_dbg, (24 + 4 * kDbgMaxWgs) * sizeof(long long)));
     E_TRY(hipMemset(e->d_dbg, 0, (24 + 4 * kDbgMaxWgs) * sizeof(long long)));
     E_TRY(hipMalloc(&e->pidx, pidx.size() * sizeof(int32_t)));
     E_TRY(hipMemcpy(e->pidx, pidx.data(), pidx.size() * sizeof(int32_t),
                     hipMemcpyHostToDevice));
-    // variant 2 needs Rc in {256, 288}
-    const bool c_ok = e->Rc == 256 || e->Rc == 288;
-    // default: conv32mt / conv32m where the geometry allows them (33^3: yes), else
-    // conv32d, else the exact-f32 kernels (conv32c, or conv32 for any FoV that
-    // fits the LDS at all)
-    e->exact_variant = c_ok ? 2 : 0;
-    e->conv_variant = e->t_ok ? 9 : e->m_ok ? 8 : e->d_ok ? 6 : e->exact_variant;
+  }
+  // The residency halves of flow_fits and h_ok: what the geometry allows
+  // (ffn_stack_plan.h) and THIS device can hold.
+  E_TRY(hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id));
+  if (caps.t_ok && depth >= 2) {
     // a single-FoV step of conv32mt runs its convs as ONE resident launch --
     // where the device can hold all of its workgroups at once: they wait for
     // each other, so one that is not on the chip stalls the rest until their
     // polls give up (a partitioned device, fewer CUs than main chunks)
-    if (e->t_ok && depth >= 2) {
-      int cus = 0, per_cu = 0;
-      E_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id));
-      E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
-      E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32ps_kernel,
-                                                         kDThreads, kMLdsBytes));
-      ConvTailMap mp;
-      tail_map(e, 1, mp);
-      const int grid = 8 * (mp.mains_per_xcd + mp.tails_per_xcd);
-      e->flow_fits = cus >= e->n_main && (long)cus * per_cu >= grid;
-    }
-    e->flow = e->flow_fits ? 2 : 0;
+    int per_cu = 0;
+    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
+    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32ps_kernel,
+                                                       kDThreads, kMLdsBytes));
+    ConvTailMap mp;
+    tail_map(e, 1, mp);
+    const int grid = 8 * (mp.mains_per_xcd + mp.tails_per_xcd);
+    e->flow_fits = e->cus >= caps.n_main && (long)e->cus * per_cu >= grid;
     // conv32hs (variant 10): 80-voxel workgroups, two per CU, all resident at once
-    if (e->t_ok && depth >= 2) {
-      const Geom& q = e->gp;
-      e->n_half = FFN_H_VCLIP ? FFN_H_VCLIP / kHChunk : (q.V + kHChunk - 1) / kHChunk;
-      const int span_h = chunk_span(q, 0, kHChunk, e->n_half);
-      int cus = 0, per_cu = 0;
-      E_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id));
-      e->cus = cus;
-      E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32hs_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kHLdsBytes));
-      E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32hs_kernel, kDThreads,
-                                                         kHLdsBytes));
-      ConvHalfMap mp;
-      half_map(e, mp);
-      e->h_ok = e->n_half >= 2 && span_h + 2 * (q.XS + 1) <= kHRows &&
-                (long)cus * per_cu >= 8 * (mp.per_first + mp.per_second);
-    }
+    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32hs_kernel),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kHLdsBytes));
+    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32hs_kernel, kDThreads,
+                                                       kHLdsBytes));
+    ConvHalfMap hm;
+    half_map(e, hm);
+    e->h_ok = caps.h_geom_ok && (long)e->cus * per_cu >= 8 * (hm.per_first + hm.per_second);
   }
+  e->flow = e->flow_fits ? 2 : 0;
 
   // weights: [w0a 27*2*32][b0a 32] ([wpack 27*32*32][bias 32]) x (2*depth-1)
   // [wl 32 + 1]
@@ -1216,13 +999,13 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
     E_TRY(hipMalloc(&e->range_flag_alt, 2 * sizeof(unsigned)));
     E_TRY(hipMemset(e->range_flag_alt, 0, 2 * sizeof(unsigned)));
     {
-      const size_t words = ((size_t)(e->gp.V + 31) / 32 + 64) * kFlowStride;
+      const size_t words = ((size_t)(g.V + 31) / 32 + 64) * kFlowStride;
       E_TRY(hipMalloc(&e->flow_flags, words * sizeof(unsigned)));
       E_TRY(hipMemset(e->flow_flags, 0, words * sizeof(unsigned)));
       E_TRY(hipMalloc(&e->flow_err, sizeof(unsigned)));
       E_TRY(hipMemset(e->flow_err, 0, sizeof(unsigned)));
-      if (e->t_ok) {
-        e->flow_trace_slots = std::max(e->n_main + e->n_tail, (e->gp.V + kHChunk - 1) / kHChunk);
+      if (caps.t_ok) {
+        e->flow_trace_slots = std::max(caps.n_main + caps.n_tail, (g.V + kHChunk - 1) / kHChunk);
         const size_t bytes = (size_t)e->flow_trace_slots * kFlowTraceLayers * 8 * sizeof(long long);
         E_TRY(hipMalloc(&e->flow_trace, bytes));
         E_TRY(hipMemset(e->flow_trace, 0, bytes));
@@ -1241,18 +1024,18 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
   for (auto& ev : e->ahead_ev) E_TRY(hipEventCreate(&ev));
 
   {
-    int rc = set_lds_attr<false, false, false>(e->lds_bytes);
-    if (!rc) rc = set_lds_attr<true, true, false>(e->lds_bytes);
-    if (!rc) rc = set_lds_attr<false, false, true>(e->lds_bytes);
-    if (!rc) rc = set_lds_attr_c<false, false, false>(e->lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<true, true, false>(e->lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true>(e->lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 8>(e->lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 16>(e->lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 24>(e->lds_bytes_c);
-    if (!rc && e->d_ok) rc = set_lds_attr_d(e->lds_bytes_d);
-    if (!rc && e->e_ok) rc = set_lds_attr_e(e->lds_bytes_e);
-    if (!rc && e->m_ok) rc = set_lds_attr_m();
+    int rc = set_lds_attr<false, false, false>(caps.lds_bytes);
+    if (!rc) rc = set_lds_attr<true, true, false>(caps.lds_bytes);
+    if (!rc) rc = set_lds_attr<false, false, true>(caps.lds_bytes);
+    if (!rc) rc = set_lds_attr_c<false, false, false>(caps.lds_bytes_c);
+    if (!rc) rc = set_lds_attr_c<true, true, false>(caps.lds_bytes_c);
+    if (!rc) rc = set_lds_attr_c<false, false, true>(caps.lds_bytes_c);
+    if (!rc) rc = set_lds_attr_c<false, false, true, 8>(caps.lds_bytes_c);
+    if (!rc) rc = set_lds_attr_c<false, false, true, 16>(caps.lds_bytes_c);
+    if (!rc) rc = set_lds_attr_c<false, false, true, 24>(caps.lds_bytes_c);
+    if (!rc && caps.d_ok) rc = set_lds_attr_d(caps.lds_bytes_d);
+    if (!rc && caps.e_ok) rc = set_lds_attr_e(caps.lds_bytes_e);
+    if (!rc && caps.m_ok) rc = set_lds_attr_m();
     if (rc) {
       ffn_engine_destroy(e);
       return rc;
@@ -1293,36 +1076,15 @@ void ffn_engine_destroy(ffn_engine* e) {
     if (ev) (void)hipEventDestroy(ev);
   for (auto& ev : e->ahead_ev)
     if (ev) (void)hipEventDestroy(ev);
-  (void)hipFree(e->act_base);
-  (void)hipFree(e->up_image);
-  (void)hipFree(e->up_seed);
-  (void)hipFree(e->seed_raw);
-  (void)hipFree(e->seed_raw_alt);
-  (void)hipFree(e->range_flag_alt);
-  (void)hipFree(e->d_spec_choice_alt);
-  (void)hipFree(e->logits);
-  (void)hipFree(e->count);
-  (void)hipFree(e->wpackd);
-  (void)hipFree(e->wpackh);
-  (void)hipFree(e->range_flag);
-  (void)hipFree(e->flow_flags);
-  (void)hipFree(e->flow_err);
-  (void)hipFree(e->flow_trace);
-  (void)hipFree(e->d_spec_choice);
-  (void)hipFree(e->d_stamps);
-  (void)hipFree(e->valid);
-  (void)hipFree(e->validbits);
-  (void)hipFree(e->pidx);
-  (void)hipFree(e->d_dbg);
-  (void)hipFree(e->weights);
-  (void)hipFree(e->d_items);
-  (void)hipFree(e->d_scratch);
-  (void)hipFree(e->d_turn);
-  if (e->h_turn) (void)hipHostFree(e->h_turn);
-  if (e->h_io) (void)hipHostFree(e->h_io);
-  if (e->h_items) (void)hipHostFree(e->h_items);
-  if (e->h_pub) (void)hipHostFree(e->h_pub);
-  if (e->h_scratch) (void)hipHostFree(e->h_scratch);
+  void* const device_mem[] = {
+      e->act_base, e->up_image, e->up_seed, e->seed_raw, e->seed_raw_alt, e->range_flag_alt,
+      e->d_spec_choice_alt, e->logits, e->count, e->wpackd, e->wpackh, e->range_flag,
+      e->flow_flags, e->flow_err, e->flow_trace, e->d_spec_choice, e->d_stamps, e->valid,
+      e->validbits, e->pidx, e->d_dbg, e->weights, e->d_items, e->d_scratch, e->d_turn};
+  for (void* p : device_mem) (void)hipFree(p);
+  void* const pinned[] = {e->h_turn, e->h_io, e->h_items, e->h_pub, e->h_scratch};
+  for (void* p : pinned)
+    if (p) (void)hipHostFree(p);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1350,8 +1112,9 @@ std::map<PaceKey, PaceVal> g_pace_cache;
 int tune_pace(ffn_engine* e) {
   e->pace_auto = 0;
   e->pace_auto_us[0] = e->pace_auto_us[1] = 0.f;
-  if (!(e->t_ok && e->flow_fits && e->flow == 2 && e->conv_variant == 9 && e->depth >= 2))
-    return FFN_OK;
+  // (only where a single FoV's stack is conv32ps: conv_variant 9 with flow = 2, which the
+  // option setters grant only where the geometry and the device admit them)
+  if (!resident_mt(plan_for(e, 1, 0))) return FFN_OK;
   const PaceKey key{e->device, e->depth, e->g.V};
   {
     std::lock_guard<std::mutex> lk(g_pace_mu);
@@ -1466,7 +1229,7 @@ int ffn_engine_set_weights(ffn_engine* e, const float* blob, size_t count) {
   for (int t = 0; t < 27; ++t) {
     const int kp[3] = {t / 9, (t / 3) % 3, t % 3};
     int ko[3];
-    for (int a = 0; a < 3; ++a) ko[e->gp.oa[a]] = kp[a];
+    for (int a = 0; a < 3; ++a) ko[e->caps.gp.oa[a]] = kp[a];
     tap_of[t] = ko[0] * 9 + ko[1] * 3 + ko[2];
   }
   std::memcpy(&host[e->w0a_off], src, sizeof(float) * 27 * 2 * F);
@@ -1537,7 +1300,7 @@ int ffn_engine_set_weights(ffn_engine* e, const float* blob, size_t count) {
   e->d_weights_ok = d_weights_ok;
   e->fp16_ok = weights_in_fp16_range;
   if ((!e->fp16_ok || !e->d_weights_ok) && e->conv_variant >= 6) {
-    int rc = switch_variant(e, e->exact_variant);
+    int rc = switch_variant(e, e->caps.exact_variant);
     if (rc) return rc;
   }
   std::memcpy(&host[e->wl_off], src, sizeof(float) * (F + 1));
@@ -1556,9 +1319,7 @@ int ffn_predict(ffn_engine* e, int n, const float* seed, const float* image,
                 float* logits_out) {
   EngineLock lock_(e);
   if (!e || !seed || !image || !logits_out) return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1 || n > e->max_batch)
-    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
-  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  if (int rc = check_batch(e, n)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t bytes = (size_t)n * e->g.V * sizeof(float);
   // through engine-owned pinned buffers: a pageable hipMemcpy costs ~80 us each
@@ -1569,37 +1330,11 @@ int ffn_predict(ffn_engine* e, int n, const float* seed, const float* image,
   std::memcpy(h_image, image, bytes);
   HIP_TRY(hipMemcpyAsync(e->up_seed, h_seed, bytes, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->up_image, h_image, bytes, hipMemcpyHostToDevice, e->stream));
-  StepItems si;
-  int rc = dense_items(e, n, &si);
-  if (rc) return rc;
-  // NaNs in a caller-provided seed stay NaN (the reference would feed them to TF).
-  rc = run_stack(e, n, si, std::nanf(""), INFINITY);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h_logits, e->logits, bytes, hipMemcpyDeviceToHost,
-                         e->stream));
-  // A void run is repeated: after a time-out of the resident launch with per-layer
-  // launches of the same kernels (same bits), after a range error -- also one that
-  // only shows in that repeat -- with the exact-f32 kernel.  At most two repeats.
-  for (int attempt = 0;; ++attempt) {
-    unsigned flag[2] = {0, 0};
-    if (e->conv_variant >= 6)
-      HIP_TRY(hipMemcpyAsync(flag, e->range_flag, sizeof(flag), hipMemcpyDeviceToHost,
-                             e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const bool is_void = e->conv_variant >= 6 && flag[0] == e->range_tag;
-    if (!is_void) {
-      if (e->last_stack_resident) e->flow_strikes = 0;
-      break;
-    }
-    if (attempt == 2) return fail(FFN_ERR_HIP, "ffn_predict: the step stayed void");
-    if (flow_voided(e, flag[1] == e->range_tag) == 0) {
-      rc = switch_variant(e, e->exact_variant);
-      if (rc) return rc;
-    }
-    rc = run_stack(e, n, si, std::nanf(""), INFINITY);
-    if (rc) return rc;
+  const int rc = predict_uploaded(e, n, "ffn_predict", [&]() -> int {
     HIP_TRY(hipMemcpyAsync(h_logits, e->logits, bytes, hipMemcpyDeviceToHost, e->stream));
-  }
+    return FFN_OK;
+  });
+  if (rc) return rc;
   std::memcpy(logits_out, h_logits, bytes);
   return FFN_OK;
 }
@@ -1609,40 +1344,16 @@ int ffn_predict_device(ffn_engine* e, int n, const float* seed_dev,
   EngineLock lock_(e);
   if (!e || !seed_dev || !image_dev || !logits_dev)
     return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1 || n > e->max_batch)
-    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
-  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  if (int rc = check_batch(e, n)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t bytes = (size_t)n * e->g.V * sizeof(float);
   HIP_TRY(hipMemcpyAsync(e->up_seed, seed_dev, bytes, hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->up_image, image_dev, bytes, hipMemcpyDeviceToDevice,
                          e->stream));
-  StepItems si;
-  int rc = dense_items(e, n, &si);
-  if (rc) return rc;
-  rc = run_stack(e, n, si, std::nanf(""), INFINITY);
-  if (rc) return rc;
-  // The same repeats of a void run as in ffn_predict; the logits leave the engine
-  // only once a run has counted, so logits_dev may be one of the inputs.
-  for (int attempt = 0;; ++attempt) {
-    unsigned flag[2] = {0, 0};
-    if (e->conv_variant >= 6)
-      HIP_TRY(hipMemcpyAsync(flag, e->range_flag, sizeof(flag), hipMemcpyDeviceToHost,
-                             e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const bool is_void = e->conv_variant >= 6 && flag[0] == e->range_tag;
-    if (!is_void) {
-      if (e->last_stack_resident) e->flow_strikes = 0;
-      break;
-    }
-    if (attempt == 2) return fail(FFN_ERR_HIP, "ffn_predict_device: the step stayed void");
-    if (flow_voided(e, flag[1] == e->range_tag) == 0) {
-      rc = switch_variant(e, e->exact_variant);
-      if (rc) return rc;
-    }
-    rc = run_stack(e, n, si, std::nanf(""), INFINITY);
-    if (rc) return rc;
-  }
+  // the logits leave the engine only once a run has counted, so logits_dev may be one
+  // of the inputs
+  if (int rc = predict_uploaded(e, n, "ffn_predict_device", [] { return (int)FFN_OK; }))
+    return rc;
   HIP_TRY(hipMemcpyAsync(logits_dev, e->logits, bytes, hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return FFN_OK;
@@ -1651,9 +1362,7 @@ int ffn_predict_device(ffn_engine* e, int n, const float* seed_dev,
 int ffn_forward_resident(ffn_engine* e, int n, int repeats) {
   EngineLock lock_(e);
   if (!e) return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1 || n > e->max_batch)
-    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
-  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  if (int rc = check_batch(e, n)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   StepItems si;
   int rc = dense_items(e, n, &si);
@@ -1705,9 +1414,7 @@ int ffn_canvas_step_submit(ffn_engine* e, int n, ffn_canvas* const* canvases,
   EngineLock lock_(e);
   if (!e || !canvases || !requests || !params || !ticket)
     return fail(FFN_ERR_ARG, "null argument");
-  if (n < 1 || n > e->max_batch)
-    return fail(FFN_ERR_ARG, "batch %d outside [1, %d]", n, e->max_batch);
-  if (!e->weights_set) return fail(FFN_ERR_STATE, "weights not set");
+  if (int rc = check_batch(e, n)) return rc;
   // the slot after the last one used, else the other one (two host threads
   // need not alternate)
   const int slot = e->slot_n[e->next_slot] == 0 ? e->next_slot : e->next_slot ^ 1;
@@ -1824,10 +1531,8 @@ int ffn_canvas_step_submit(ffn_engine* e, int n, ffn_canvas* const* canvases,
     e->stat_ahead_used += 1;
     if (e->ahead_ev_pending) {  // its event pair is a stack's: among the samples from now on
       e->ahead_ev_pending = false;
-      if (e->events_used + 2 > (int)e->events.size()) {
-        rc = flush_events(e);
-        if (rc) return rc;
-      }
+      rc = event_pair(e);
+      if (rc) return rc;
       e->chain_launches_pending.push_back(2 * e->depth - 1);
       std::swap(e->events[e->events_used++], e->ahead_ev[0]);
       std::swap(e->events[e->events_used++], e->ahead_ev[1]);
@@ -1884,21 +1589,18 @@ int ffn_canvas_step_submit(ffn_engine* e, int n, ffn_canvas* const* canvases,
     const int paste_blocks = e->paste_blocks > 0
         ? e->paste_blocks
         : std::max(kPasteBlocksMin, std::min(kPasteBlocks, e->cus - 1 - tiles));
-    // (experiment debug_fused_twice: the same launch made twice -- idempotent: same record,
-    // same paste, same conv0_a -- so that the second, traced one starts on warm caches)
-    if (e->debug_fused_twice)
+    const auto fused = [&](int trace) {
       hipLaunchKernelGGL(faces_paste_conv0a_kernel, dim3(1 + paste_blocks + tiles),
                          dim3(512), 0, e->stream, si, g, e->logits, e->seed_raw, e->count,
                          e->count_blocks, params->move_threshold,
                          params->disco_seed_threshold, params->deleted_threshold,
                          e->range_flag, e->range_tag, h_pub, step_id, e->d_spec_choice,
-                         spec_expected, nx, e->d_stamps, 0, paste_blocks);
-    hipLaunchKernelGGL(faces_paste_conv0a_kernel, dim3(1 + paste_blocks + tiles),
-                       dim3(512), 0, e->stream, si, g, e->logits, e->seed_raw, e->count,
-                       e->count_blocks, params->move_threshold,
-                       params->disco_seed_threshold, params->deleted_threshold,
-                       e->range_flag, e->range_tag, h_pub, step_id, e->d_spec_choice,
-                       spec_expected, nx, e->d_stamps, e->trace_now ? 1 : 0, paste_blocks);
+                         spec_expected, nx, e->d_stamps, trace, paste_blocks);
+    };
+    // (experiment debug_fused_twice: the same launch made twice -- idempotent: same record,
+    // same paste, same conv0_a -- so that the second, traced one starts on warm caches)
+    if (e->debug_fused_twice) fused(0);
+    fused(e->trace_now ? 1 : 0);
   } else if (n == 1 && e->fuse_paste) {
     hipLaunchKernelGGL(faces_paste_kernel, dim3(1 + 71), dim3(512), 0, e->stream, si,
                        g, e->logits, e->seed_raw, e->count, e->count_blocks,
@@ -1922,7 +1624,7 @@ int ffn_canvas_step_submit(ffn_engine* e, int n, ffn_canvas* const* canvases,
       // stack was a resident launch that is still trusted, and the loop made the step
       bool ahead = false;
       if (fused_next && e->stack_ahead && from_loop && this_stack_resident &&
-          e->flow == 2 && e->flow_skip == 0 && e->conv_variant == 9) {
+          resident_mt(plan_for(e, 1, e->flow_skip))) {
         rc = run_stack(e, 1, si, params->pad_value, params->move_threshold, true, true);
         if (rc) return rc;
         ahead = true;
@@ -2099,6 +1801,23 @@ int ffn_canvas_step(ffn_engine* e, int n, ffn_canvas* const* canvases,
 }
 
 namespace {
+// What the segment calls check per canvas; k: the canvas' index in a batched call, whose
+// messages name it (-1: the call has one canvas).
+int check_segment_params(const ffn_canvas* c, const ffn_segment_params& p, int resume, int k) {
+  if (p.prefetch < 0 || p.prefetch > FFN_MAX_CANDIDATES)
+    return fail(FFN_ERR_ARG, "prefetch must be 0..%d", FFN_MAX_CANDIDATES);
+  if (p.shape_zyx[0] != c->cz || p.shape_zyx[1] != c->cy || p.shape_zyx[2] != c->cx)
+    return k < 0 ? fail(FFN_ERR_ARG, "shape_zyx does not match the canvas")
+                 : fail(FFN_ERR_ARG, "shape_zyx does not match canvas %d", k);
+  for (int a = 0; a < 3; ++a)
+    if (p.deltas_zyx[a] < 0 || p.margin_zyx[a] < 0)
+      return fail(FFN_ERR_ARG, "negative deltas / margin");
+  if (resume && !c->loop.active)
+    return k < 0 ? fail(FFN_ERR_STATE, "no segment to resume")
+                 : fail(FFN_ERR_STATE, "canvas %d: no segment to resume", k);
+  return FFN_OK;
+}
+
 // the HIP canvas as the device of the host loop
 struct HipLoopDevice {
   ffn_canvas* c;
@@ -2156,16 +1875,7 @@ int ffn_canvas_segment_at(ffn_canvas* c, const int32_t start[3],
   if (!c || !start || !p || !out) return fail(FFN_ERR_ARG, "null argument");
   if (!c->engine) return fail(FFN_ERR_STATE, "canvas outlived its engine");
   if (int rc = resolve_many_carry(c->engine, c)) return rc;
-  if (p->prefetch < 0 || p->prefetch > FFN_MAX_CANDIDATES)
-    return fail(FFN_ERR_ARG, "prefetch must be 0..%d", FFN_MAX_CANDIDATES);
-  if (p->shape_zyx[0] != c->cz || p->shape_zyx[1] != c->cy ||
-      p->shape_zyx[2] != c->cx)
-    return fail(FFN_ERR_ARG, "shape_zyx does not match the canvas");
-  for (int a = 0; a < 3; ++a)
-    if (p->deltas_zyx[a] < 0 || p->margin_zyx[a] < 0)
-      return fail(FFN_ERR_ARG, "negative deltas / margin");
-  if (resume && !c->loop.active)
-    return fail(FFN_ERR_STATE, "no segment to resume");
+  if (int rc = check_segment_params(c, *p, resume, -1)) return rc;
   HipLoopDevice dev{c};
   ffn_host::SegmentLoop<HipLoopDevice> loop(dev, c->loop, *p);
   return loop.run(start, resume, out);
@@ -2197,15 +1907,7 @@ int ffn_canvas_segment_many_carry(ffn_engine* e, int n, ffn_canvas* const* canva
     for (int k2 = 0; k2 < k; ++k2)
       if (canvases[k2] == c) return fail(FFN_ERR_ARG, "canvas appears twice");
     const ffn_segment_params& p = params[k];
-    if (p.prefetch < 0 || p.prefetch > FFN_MAX_CANDIDATES)
-      return fail(FFN_ERR_ARG, "prefetch must be 0..%d", FFN_MAX_CANDIDATES);
-    if (p.shape_zyx[0] != c->cz || p.shape_zyx[1] != c->cy || p.shape_zyx[2] != c->cx)
-      return fail(FFN_ERR_ARG, "shape_zyx does not match canvas %d", k);
-    for (int a = 0; a < 3; ++a)
-      if (p.deltas_zyx[a] < 0 || p.margin_zyx[a] < 0)
-        return fail(FFN_ERR_ARG, "negative deltas / margin");
-    if (resume[k] && !c->loop.active)
-      return fail(FFN_ERR_STATE, "canvas %d: no segment to resume", k);
+    if (int rc = check_segment_params(c, p, resume[k], k)) return rc;
     if (std::memcmp(&p.step, &params[0].step, sizeof(ffn_step_params)) != 0)
       return fail(FFN_ERR_ARG, "canvas %d: step parameters differ from canvas 0's", k);
     devs[k].c = c;

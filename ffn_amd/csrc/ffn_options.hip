@@ -36,7 +36,7 @@ namespace {
 // ---- the options whose set is more than a field store ----
 
 int set_conv_variant(ffn_engine* e, int value) {
-  if (value == -1) value = e->exact_variant;  // "the exact-f32 kernel of this FoV"
+  if (value == -1) value = e->caps.exact_variant;  // "the exact-f32 kernel of this FoV"
   if (value != 0 && value != 2 && !(value >= 6 && value <= 10))
     return fail(FFN_ERR_ARG, "conv_variant must be 0, 2, 6, 7, 8, 9 or 10 (1, 3, 4, 5 "
                              "were removed in ABI 7)");
@@ -46,18 +46,18 @@ int set_conv_variant(ffn_engine* e, int value) {
   if (value >= 6 && e->weights_set && !e->fp16_ok)
     return fail(FFN_ERR_ARG, "conv_variant %d: a weight is outside the fp16 range",
                 value);
-  if (value == 6 && !e->d_ok)
+  if (value == 6 && !e->caps.d_ok)
     return fail(FFN_ERR_ARG, "conv_variant 6 unsupported for this fov / depth");
-  if (value == 7 && !e->e_ok)
+  if (value == 7 && !e->caps.e_ok)
     return fail(FFN_ERR_ARG, "conv_variant 7 unsupported for this fov / depth");
-  if (value == 8 && !e->m_ok)
+  if (value == 8 && !e->caps.m_ok)
     return fail(FFN_ERR_ARG, "conv_variant 8 unsupported for this fov / depth");
-  if (value == 9 && !e->t_ok)
+  if (value == 9 && !e->caps.t_ok)
     return fail(FFN_ERR_ARG, "conv_variant 9 unsupported for this fov / depth "
                              "(257 .. 512 chunks of 128 voxels)");
   if (value >= 6 && e->weights_set && !e->d_weights_ok)
     return fail(FFN_ERR_ARG, "conv_variant 6: a weight x 2^11 is outside the fp16 range");
-  if (value == 2 && !(e->Rc == 256 || e->Rc == 288))
+  if (value == 2 && !(e->caps.Rc == 256 || e->caps.Rc == 288))
     return fail(FFN_ERR_ARG, "conv_variant %d unsupported for this fov", value);
   return switch_variant(e, value);
 }
@@ -66,7 +66,7 @@ int set_conv_variant(ffn_engine* e, int value) {
 // launches with the flagged hand-off compiled in; 2 the resident stack (conv32ps: one
 // launch for all convs).  Same bits in every mode.
 int set_flow(ffn_engine* e, int value) {
-  if (value && !e->t_ok)
+  if (value && !e->caps.t_ok)
     return fail(FFN_ERR_ARG, "flow needs conv32mt's geometry (conv_variant 9)");
   if (value && e->depth < 2) return fail(FFN_ERR_ARG, "flow needs depth >= 2");
   if (value == 2 && !e->flow_fits)
@@ -215,7 +215,7 @@ const Option kOptions[] = {
     {"fuse_head", &E::fuse_head, 0, 0, kOnOff},
     {"fuse_paste", &E::fuse_paste, 0, 0, kOnOff},
     {"fuse_conv0a", &E::fuse_conv0a, 0, 0, kOnOff | kDrop},
-    {"exact_variant", &E::exact_variant, 0, 0, kReadOnly},
+    derived("exact_variant", FFN_GET(e->caps.exact_variant)),
     {"flow_auto_off", &E::flow_auto_off, 0, 0, kReadOnly},
     // the lab: pacing, ablation, tracing
     {"paste_blocks", &E::paste_blocks, 0, 1024},

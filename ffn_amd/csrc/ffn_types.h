@@ -29,6 +29,35 @@ constexpr int kTile = 16;            // positions per MFMA M-tile
 constexpr int kTilesPerWave = 5;     // 2 tile groups x 5 tiles = 10 tiles = kChunk
 constexpr int kConvThreads = 256;    // 4 waves: (nhalf, tile group)
 
+// Chunk sizes, LDS rows and LDS bytes of the conv kernel families: what the host's
+// arithmetic on a FoV (ffn_stack_plan.h) shares with the kernels that use them.
+// conv32c (ffn_conv_exact.h)
+constexpr int kCChunk = 144;
+constexpr int kCLdsStride = 40;      // LDS row stride in floats: 32 channels + 8 pad
+// conv32d (ffn_conv_split.h), and its 96-voxel form (conv_variant 7)
+constexpr int kDChunk = 160;
+constexpr int kDThreads = 256;
+constexpr int kDRowB = 144;          // epilogue: row stride of the partial sums in LDS
+constexpr int kERows = 208, kETiles = 3, kEPieces = 7;
+// conv32m
+constexpr int kMChunk = 128;
+constexpr int kMRows = 240;
+constexpr int kMSeg = 8 * kMRows * 16;         // bytes of a segment slot
+constexpr int kMRing = 2 * kMSeg;              // LDS offset of the weight ring
+constexpr int kMRingTaps = 5;                  // taps resident in the weight ring
+constexpr int kMLdsBytes = kMRing + kMRingTaps * 4096;  // 81,920: two per CU
+// conv32mt's tail workgroups: rows per dz segment
+constexpr int kTRows = 144;          // TNT = 1
+constexpr int kT3Rows = 208;         // TNT = 3 (= conv_variant 7's kERows)
+// conv32h / conv32hs (ffn_conv_half.h)
+constexpr int kHChunk = 80;
+constexpr int kHRows = 192;  // 80 voxels + 3 row ends + one plane end (XS) + 2 (XS + 1), XS <= 34
+constexpr int kHSeg = 8 * kHRows * 16;            // bytes of a segment slot (24 DMA pieces)
+constexpr int kHRingOff = 2 * kHSeg;
+constexpr int kHUnit = 4 * 4096;                  // four taps of weight fragments
+constexpr int kHLdsBytes = kHRingOff + 2 * kHUnit;  // 81,920: two per CU
+constexpr int kHeadBlocks = 281;  // head kernel grid.x (4 sweeps of 32 voxels x 281)
+
 struct Geom {
   int fz, fy, fx;      // FoV (zyx)
   int dz, dy, dx;      // deltas (zyx)
