@@ -421,8 +421,12 @@ __device__ __forceinline__ void split8_fp16(const f32x4& v0, const f32x4& v1,
 // (1, 144, 2) with KS = 5: a single 32-voxel tile, the form of conv32mt's tail.
 // The workgroup computes the 32 NT dense voxels from v0 of FoV `item`; gc = its
 // slot in head_count; aoff_tab = a.aoff or the table of another row count.
+// PROD = 1 (engine option mfma_products, conv32mt's tail only): hi x hi alone --
+// no cross-product MFMA, no LDS read of a residual plane.  Staging and the memory
+// queue are PROD = 3's (the residual weight fragments are still fetched and
+// waited for where their MFMA stood), so every hand-placed vmcnt holds as it is.
 template <int KIND, bool ADD_SKIP, int KS, bool HEAD, int NT, int R, int WPS,
-          bool FLOW = false>
+          bool FLOW = false, int PROD = 3>
 __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer& L,
                                              const int item,
                                              const int v0, const int gc,
@@ -430,6 +434,7 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
   typedef f16x8 frag_t;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   static_assert(NT == 5 || NT == 3 || NT == 1, "tile loop: 5, 3 or 1 tiles");
+  static_assert(PROD == 3 || (PROD == 1 && !FLOW), "three products, or one without FLOW");
   static_assert(!FLOW || WPS > 1, "FLOW: the everything-up-front issue order");
   static_assert(4 * KS * 64 >= 8 * R && R % 8 == 0, "KS pieces per wave cover a slot");
   constexpr int kChunkD = 32 * NT;  // dense voxels per workgroup
@@ -576,7 +581,7 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
   auto loadX = [&](int t, int off, XFragD& dst) {
     const char* p = ldsb + xb[t] + off;
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
+    for (int pl = 0; pl < (PROD == 3 ? 2 : 1); ++pl)
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh)
         dst.x[kh][pl] =
@@ -611,12 +616,16 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
   PREFETCH;                                                                   \
   EXTRA;                                                                      \
   __builtin_amdgcn_sched_barrier(0);                                          \
-  accC[T] = mma(WCUR.w[0][0], XCUR.x[0][1], accC[T]);                         \
+  if constexpr (PROD == 3) accC[T] = mma(WCUR.w[0][0], XCUR.x[0][1], accC[T]); \
   acc[T] = mma(WCUR.w[0][0], XCUR.x[0][0], acc[T]);                           \
-  accC[T] = mma(WCUR.w[0][1], XCUR.x[0][0], accC[T]);                         \
+  if constexpr (PROD == 3) accC[T] = mma(WCUR.w[0][1], XCUR.x[0][0], accC[T]); \
   acc[T] = mma(WCUR.w[1][0], XCUR.x[1][0], acc[T]);                           \
-  accC[T] = mma(WCUR.w[1][0], XCUR.x[1][1], accC[T]);                         \
-  accC[T] = mma(WCUR.w[1][1], XCUR.x[1][0], accC[T]);
+  if constexpr (PROD == 3) {                                                  \
+    accC[T] = mma(WCUR.w[1][0], XCUR.x[1][1], accC[T]);                       \
+    accC[T] = mma(WCUR.w[1][1], XCUR.x[1][0], accC[T]);                       \
+  } else { /* (the fetched residual fragments stay in the memory queue) */    \
+    asm volatile("" ::"v"(WCUR.w[0][1]), "v"(WCUR.w[1][1]));                  \
+  }
   // tap J of the wave (XA holds tile 0's fragments on entry); CONT: prefetch
   // tile 0 of the next tap under the last tile (false in front of a barrier);
   // E0..E4: the extra memory instructions of its five tiles
@@ -740,8 +749,14 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
     for (int t = 0; t < NT; ++t) {
       // tile by tile (the scheduler would otherwise pull every accumulator out
       // of the AGPRs at once and spill the kernel's long-lived values)
-      asm volatile("" : "+a"(acc[t]), "+a"(accC[t]));  // still AGPRs here
-      const f32x16 s = acc[t] + accC[t] * 4.8828125e-4f;  // 2^-11
+      f32x16 s;
+      if constexpr (PROD == 3) {
+        asm volatile("" : "+a"(acc[t]), "+a"(accC[t]));  // still AGPRs here
+        s = acc[t] + accC[t] * 4.8828125e-4f;  // 2^-11
+      } else {
+        asm volatile("" : "+a"(acc[t]));
+        s = acc[t];
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         *reinterpret_cast<f32x4*>(P + t * (32 * kDRowB) + g * 32) =
@@ -962,7 +977,12 @@ __device__ __forceinline__ f32x4 hidden_load16f(const char* sbase, unsigned voff
 // stays in `xres` (the lane / register layout of the accumulators, the same in
 // every conv of the stack) instead of going through memory: conv_b neither
 // loads its skip operand nor stores X -- 9.2 MB less per conv_b.
-template <int KIND, bool ADD_SKIP, bool HEAD, bool FLOW = false, bool RES = false>
+// PROD = 1 (engine option mfma_products): hi x hi alone -- per tap two MFMAs
+// instead of six and four LDS fragment reads instead of eight, the epilogue
+// takes `acc` as it is.  Staging, the weight ring, m_wait and the barriers are
+// PROD = 3's: all eight planes and the 4-KB taps are still copied.
+template <int KIND, bool ADD_SKIP, bool HEAD, bool FLOW = false, bool RES = false,
+          int PROD = 3>
 __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer& L,
                                              const int item,
                                              const int v0, const int gc,
@@ -971,6 +991,8 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
   typedef f16x8 frag_t;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+  static_assert(PROD == 3 || (PROD == 1 && !FLOW && !RES),
+                "three products, or one in a plain per-layer launch");
   constexpr int R = kMRows;
   constexpr int R16 = R * 16;
   constexpr bool kSkipLoad = ADD_SKIP && !RES;
@@ -1061,12 +1083,14 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
     const int kz = s / 9, ky = (s / 3) % 3, kx = s % 3;
     const char* px = ldsb + xb + (kz & 1) * kMSeg + ((ky - 1) * a.XS + (kx - 1)) * 16;
     f.x[kh][0] = *reinterpret_cast<const frag_t*>(px + (0 * 4 + kh * 2) * R16);
-    f.x[kh][1] = *reinterpret_cast<const frag_t*>(px + (1 * 4 + kh * 2) * R16);
+    if constexpr (PROD == 3)
+      f.x[kh][1] = *reinterpret_cast<const frag_t*>(px + (1 * 4 + kh * 2) * R16);
   };
   auto load_w = [&](int s, int kh, WFrag& f) {  // 2 of the 4 weight reads of tap s
     const char* pw = ldsb + kMRing + (s % D) * 4096 + lane * 16;
     f.w[kh][0] = *reinterpret_cast<const frag_t*>(pw + (kh * 2 + 0) * 1024);
-    f.w[kh][1] = *reinterpret_cast<const frag_t*>(pw + (kh * 2 + 1) * 1024);
+    if constexpr (PROD == 3)
+      f.w[kh][1] = *reinterpret_cast<const frag_t*>(pw + (kh * 2 + 1) * 1024);
   };
   f32x16 acc, accC;
 #pragma unroll
@@ -1166,20 +1190,20 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
       asm volatile("" ::: "memory");                                            \
     }                                                                           \
     __builtin_amdgcn_sched_barrier(0);                                          \
-    accC = mma(WCUR.w[0][0], XCUR.x[0][1], accC);                               \
+    if constexpr (PROD == 3) accC = mma(WCUR.w[0][0], XCUR.x[0][1], accC);      \
     __builtin_amdgcn_sched_barrier(0);                                          \
     if (!(FLOW && (kAbl & 4)) && (S) > 0 && (S) + D - 1 <= 26) dma_w((S) + D - 1); \
     if (FLOW && (S) == 1) flow_late_load();                                     \
     __builtin_amdgcn_sched_barrier(0);                                          \
     acc = mma(WCUR.w[0][0], XCUR.x[0][0], acc);                                 \
     FFN_MGAP(S, 0, WNEXT, XNEXT)                                                \
-    accC = mma(WCUR.w[0][1], XCUR.x[0][0], accC);                               \
+    if constexpr (PROD == 3) accC = mma(WCUR.w[0][1], XCUR.x[0][0], accC);      \
     FFN_MGAP(S, 1, WNEXT, XNEXT)                                                \
     acc = mma(WCUR.w[1][0], XCUR.x[1][0], acc);                                 \
     FFN_MGAP(S, 2, WNEXT, XNEXT)                                                \
-    accC = mma(WCUR.w[1][0], XCUR.x[1][1], accC);                               \
+    if constexpr (PROD == 3) accC = mma(WCUR.w[1][0], XCUR.x[1][1], accC);      \
     FFN_MGAP(S, 3, WNEXT, XNEXT)                                                \
-    accC = mma(WCUR.w[1][1], XCUR.x[1][0], accC);                               \
+    if constexpr (PROD == 3) accC = mma(WCUR.w[1][1], XCUR.x[1][0], accC);      \
     __builtin_amdgcn_sched_barrier(0);                                          \
     if ((S) == 27 - D) issue_epilogue_loads();                                  \
     __builtin_amdgcn_sched_barrier(0);                                          \
@@ -1268,7 +1292,9 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
     asm volatile(""
                  : "+v"(hw4[0]), "+v"(hw4[1]), "+v"(hw4[2]), "+v"(hw4[3]),
                    "+v"(seedv));
-  const f32x16 s = acc + accC * 4.8828125e-4f;  // 2^-11
+  f32x16 s;
+  if constexpr (PROD == 3) s = acc + accC * 4.8828125e-4f;  // 2^-11
+  else s = acc;
   unsigned range_max = 0;
   if constexpr (HEAD) {
     hbias = a.head_w[kFeatures];
@@ -1375,6 +1401,20 @@ __global__ __launch_bounds__(kDThreads, 2) void conv32m_kernel(ConvDArgs a) {
   stamp_workgroup(a, a.L, t0);
 }
 
+// mfma_products = 1: the same launch with the one-product body (a kernel of its own
+// name, so that the three-product symbols and their code stay exactly as they are)
+template <int KIND, bool ADD_SKIP, bool HEAD>
+__global__ __launch_bounds__(kDThreads, 2) void conv32m1_kernel(ConvDArgs a) {
+  const int gc = (blockIdx.x & 7) * a.slots_per_xcd + (blockIdx.x >> 3);
+  if (gc >= a.total_slots) return;
+  const long long t0 = a.dbg_wgs ? wall_clock64() : 0;
+  const int item = (int)__umulhi((unsigned)gc, a.magic_nchunks);
+  const int chunk = gc - item * a.nchunks;
+  conv32m_body<KIND, ADD_SKIP, HEAD, false, false, 1>(a, a.L, item, chunk * kMChunk, gc,
+                                                      gc == 0);
+  stamp_workgroup(a, a.L, t0);
+}
+
 // ---------------------------------------------------------------------------
 // conv32mt (conv_variant 9): conv32m with a K-split tail.
 //
@@ -1451,6 +1491,49 @@ __global__ __launch_bounds__(kDThreads, 2) void conv32mt_kernel(ConvDArgs a,
     // single-FoV tail: first barrier at 4.5 K instead of 5.2 K cycles, but the
     // taps 6.9 K instead of 5.8 K: profiles/r02_wg_timeline.txt)
     conv32d_body<KIND, ADD_SKIP, kPieces, HEAD, TNT, kRows, 2, FLOW>(
+        a, a.L, item, mp.n_main * kMChunk + c * (32 * TNT), item * slots + mp.n_main + c,
+        mp.taoff, item == 0 && c == 0 && a.dbg_wgs == 2);
+  }
+  stamp_workgroup(a, a.L, t0);
+}
+
+// mfma_products = 1: conv32mt_kernel's map of workgroups, main and tail bodies with the
+// one product (no FLOW form; its own name, as conv32m1_kernel)
+template <int KIND, bool ADD_SKIP, bool HEAD, int TNT>
+__global__ __launch_bounds__(kDThreads, 2) void conv32mt1_kernel(ConvDArgs a,
+                                                                 ConvTailMap mp) {
+  const int xcd = blockIdx.x & 7;
+  const int idx = blockIdx.x >> 3;
+  int item, r;
+  bool main_wg;
+  if (TNT == 1) {
+    const int per_item = mp.mains_per_xcd + mp.tails_per_xcd;
+    item = idx / per_item;
+    r = idx - item * per_item;
+    main_wg = r < mp.mains_per_xcd;
+    if (!main_wg) r -= mp.mains_per_xcd;
+  } else {
+    const int tails = mp.n * mp.tails_per_xcd;
+    main_wg = idx >= tails;
+    const int i2 = main_wg ? idx - tails : idx;
+    const int per = main_wg ? mp.mains_per_xcd : mp.tails_per_xcd;
+    item = i2 / per;
+    r = i2 - item * per;
+  }
+  if (item >= mp.n) return;
+  const long long t0 = a.dbg_wgs ? wall_clock64() : 0;
+  const int slots = mp.n_main + mp.n_tail;
+  if (main_wg) {
+    const int c = xcd * mp.mains_per_xcd + r;
+    if (c >= mp.n_main) return;
+    conv32m_body<KIND, ADD_SKIP, HEAD, false, false, 1>(
+        a, a.L, item, c * kMChunk, item * slots + c, blockIdx.x == 0 && a.dbg_wgs != 2);
+  } else {
+    const int c = xcd * mp.tails_per_xcd + r;
+    if (c >= mp.n_tail) return;
+    constexpr int kPieces = TNT == 1 ? kTPieces : kT3Pieces;
+    constexpr int kRows = TNT == 1 ? kTRows : kT3Rows;
+    conv32d_body<KIND, ADD_SKIP, kPieces, HEAD, TNT, kRows, 2, false, 1>(
         a, a.L, item, mp.n_main * kMChunk + c * (32 * TNT), item * slots + mp.n_main + c,
         mp.taoff, item == 0 && c == 0 && a.dbg_wgs == 2);
   }

@@ -102,6 +102,7 @@ struct ffn_engine {
   float* rawS = nullptr;
   int batch_chunks = 1;   // option: variant 6 uses the 96-voxel form for n >= 2
   int tail_batched = 0;   // option: steps with >= 2 FoVs take conv32mt's tail form too
+  int mfma_products = 3;  // option: 1 = conv32m / conv32mt keep the hi x hi product alone
   // FLOW (ffn_conv_split.h "flagged launches"): 0 off; 1 conv32mt's launches with
   // the flagged hand-off compiled in (still one dependent launch per conv: the
   // words are always there already -- isolates the cost of the sc1 reads and

@@ -146,14 +146,20 @@ int set_lds_attr_m() {
 #define FFN_MTF(KIND, SK, HEADV) \
   FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 1, true>), kMLdsBytes)
 #define FFN_H(KIND, SK, HEADV) FFN_LDS_ATTR((conv32h_kernel<KIND, SK, HEADV>), kHLdsBytes)
+#define FFN_M1(KIND, SK, HEADV)                                           \
+  FFN_LDS_ATTR((conv32m1_kernel<KIND, SK, HEADV>), kMLdsBytes);           \
+  FFN_LDS_ATTR((conv32mt1_kernel<KIND, SK, HEADV, 1>), kMLdsBytes);       \
+  FFN_LDS_ATTR((conv32mt1_kernel<KIND, SK, HEADV, 3>), kMLdsBytes)
   FFN_CONV_FORMS(FFN_M);
   FFN_CONV_FORMS(FFN_MT);
+  FFN_CONV_FORMS(FFN_M1);
   FFN_CONV_FORMS4(FFN_MTF);
   FFN_CONV_FORMS4(FFN_H);
 #undef FFN_M
 #undef FFN_MT
 #undef FFN_MTF
 #undef FFN_H
+#undef FFN_M1
   FFN_LDS_ATTR(conv32hs_kernel, kHLdsBytes);
   FFN_LDS_ATTR(conv32ps_kernel, kMLdsBytes);
   return FFN_OK;
@@ -390,7 +396,8 @@ int launch_conv32d(ffn_engine* e, const StackPlan& plan, int n, const float* raw
     ConvTailMap mp;
     tail_map(e, n, mp);
     const dim3 tgrid(8 * n * (mp.mains_per_xcd + mp.tails_per_xcd));
-    const bool flow1 = one && e->flow == 1;
+    const bool one_product = plan.products == 1;  // (per-layer launches without FLOW)
+    const bool flow1 = one && e->flow == 1 && !one_product;
     if (flow1) {
       a.L.flow_wait_on = layer > 0;
       a.L.flow_wait = e->flow_epoch;
@@ -401,6 +408,13 @@ int launch_conv32d(ffn_engine* e, const StackPlan& plan, int n, const float* raw
     if constexpr (KIND == 0 || SK || !HEADV)                                      \
       hipLaunchKernelGGL((conv32mt_kernel<KIND, SK, HEADV, 1, true>), tgrid,      \
                          block, kMLdsBytes, e->stream, a, mp);                    \
+  } else if (one_product) {                                                       \
+    if (one)                                                                      \
+      hipLaunchKernelGGL((conv32mt1_kernel<KIND, SK, HEADV, 1>), tgrid, block,    \
+                         kMLdsBytes, e->stream, a, mp);                           \
+    else                                                                          \
+      hipLaunchKernelGGL((conv32mt1_kernel<KIND, SK, HEADV, 3>), tgrid, block,    \
+                         kMLdsBytes, e->stream, a, mp);                           \
   } else if (one)                                                                 \
     hipLaunchKernelGGL((conv32mt_kernel<KIND, SK, HEADV, 1>), tgrid, block,       \
                        kMLdsBytes, e->stream, a, mp);                             \
@@ -414,14 +428,19 @@ int launch_conv32d(ffn_engine* e, const StackPlan& plan, int n, const float* raw
     }
 #undef FFN_MT_LAUNCH
   } else if (plan.family == ConvFamily::M) {
+#define FFN_M_LAUNCH(HEADV)                                                      \
+  if (plan.products == 1)                                                        \
+    hipLaunchKernelGGL((conv32m1_kernel<KIND, SK, HEADV>), grid, block,          \
+                       kMLdsBytes, e->stream, a);                                \
+  else                                                                           \
+    hipLaunchKernelGGL((conv32m_kernel<KIND, SK, HEADV>), grid, block,           \
+                       kMLdsBytes, e->stream, a)
     if (head.on) {
-      if constexpr (KIND == 1)
-        hipLaunchKernelGGL((conv32m_kernel<KIND, SK, true>), grid, block,
-                           kMLdsBytes, e->stream, a);
+      if constexpr (KIND == 1) { FFN_M_LAUNCH(true); }
     } else {
-      hipLaunchKernelGGL((conv32m_kernel<KIND, SK, false>), grid, block,
-                         kMLdsBytes, e->stream, a);
+      FFN_M_LAUNCH(false);
     }
+#undef FFN_M_LAUNCH
   } else if (plan.family == ConvFamily::D96) {
     if (head.on) {
       if constexpr (KIND == 1) FFN_E_LAUNCH(true);
@@ -612,7 +631,7 @@ int launch_conv32hs(ffn_engine* e, const StackPlan& plan, float pad_value, float
 // or 0 for "once no repeat is pending").
 StackPlan plan_for(const ffn_engine* e, int n, int flow_skip) {
   return plan_stack(e->caps, e->conv_variant, e->flow, flow_skip, e->tail_batched,
-                    e->batch_chunks, n);
+                    e->batch_chunks, n, e->mfma_products);
 }
 
 // The chain of launches of a stack, one per conv: conv0_b, then per residual module

@@ -80,6 +80,16 @@ int set_flow(ffn_engine* e, int value) {
   return FFN_OK;
 }
 
+// MFMA products per fp16 operand pair in conv32m / conv32mt: 3 (the split product,
+// f32-accurate) or 1 (hi x hi alone: fp16 inference).  Stored whatever the variant;
+// plan_stack decides where it takes effect.
+int set_mfma_products(ffn_engine* e, int value) {
+  if (value != 1 && value != 3) return fail(FFN_ERR_ARG, "mfma_products must be 3 or 1");
+  drop_spec(e);
+  e->mfma_products = value;
+  return FFN_OK;
+}
+
 int set_stat_reset(ffn_engine* e, int) {
   e->stat_spec_launched = e->stat_spec_hits = e->stat_spec_mismatch = 0;
   e->stat_ahead_used = e->stat_ahead_wasted = 0;
@@ -207,6 +217,7 @@ const Option kOptions[] = {
     {"flow", &E::flow, 0, 2, 0, set_flow},
     {"batch_chunks", &E::batch_chunks, 0, 2},
     {"tail_batched", &E::tail_batched, 0, 0, kOnOff},
+    {"mfma_products", &E::mfma_products, 0, 0, 0, set_mfma_products},
     {"speculate", &E::speculate, 0, 0, kOnOff | kDrop},
     {"stack_ahead", &E::stack_ahead, 0, 0, kOnOff | kDrop},
     {"sync_mode", &E::sync_mode, 0, 1},

@@ -238,6 +238,7 @@ struct StackPlan {
   bool resident;   // ONE launch for all convs (conv32ps for MT, conv32hs for H)
   int tail_tiles;  // MT: 32-voxel tiles per tail workgroup, 1 or 3
   int chunks;      // entries per item in `count` when the head is fused
+  int products;    // MFMA products per fp16 operand pair: 3, or 1 (M and MT alone)
 };
 
 // conv32d: one workgroup per CU (160-voxel chunks) for a single FoV; with several FoVs
@@ -250,9 +251,14 @@ struct StackPlan {
 // several FoVs run plain conv32m, as under 9.
 // A resident launch is for ONE FoV, with flow = 2 and no repeat of a voided resident step
 // pending (flow_skip: the caller counts it down).
+// products (engine option mfma_products) = 1: the families M and MT keep the hi x hi
+// product alone; every other family has no such form and runs as it always does
+// (StackPlan::products says 3 for it).  The one-product kernels exist as per-layer
+// launches only, so such a plan is never resident: a single FoV runs conv32mt as it does
+// with flow = 0.
 inline StackPlan plan_stack(const ConvCaps& c, int conv_variant, int flow, int flow_skip,
-                            int tail_batched, int batch_chunks, int n) {
-  StackPlan p{ConvFamily::D160, false, 1, c.nchunks_k};
+                            int tail_batched, int batch_chunks, int n, int products = 3) {
+  StackPlan p{ConvFamily::D160, false, 1, c.nchunks_k, 3};
   if (conv_variant == 0) {
     p.family = ConvFamily::Conv32, p.chunks = 0;  // (its head is never fused)
   } else if (conv_variant < 6) {
@@ -270,8 +276,10 @@ inline StackPlan plan_stack(const ConvCaps& c, int conv_variant, int flow, int f
              (conv_variant == 6 && batch_chunks == 1 && n >= 2 && c.e_ok)) {
     p.family = ConvFamily::D96, p.chunks = c.nchunks_e;
   }
+  if (products == 1 && (p.family == ConvFamily::M || p.family == ConvFamily::MT))
+    p.products = 1;
   p.resident = (p.family == ConvFamily::MT || p.family == ConvFamily::H) && n == 1 &&
-               flow == 2 && flow_skip == 0;
+               flow == 2 && flow_skip == 0 && p.products == 3;
   return p;
 }
 

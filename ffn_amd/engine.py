@@ -218,10 +218,17 @@ class HipEngine:
   def set_option(self, name: str, value: int, explicit: bool = True):
     """ffn_engine_set_option.  conv_variant: 0 / 2 (exact f32), 6 .. 9, or -1 =
     this FoV's exact-f32 kernel; `explicit=False` is for the library's own
-    choices (the batched drivers' pin, the fp16-range fallback)."""
+    choices (the batched drivers' pin, the fp16-range fallback).
+    mfma_products: 3 (default) or 1 = fp16 inference in conv32m / conv32mt
+    (include/ffn_hip.h; outside the f32 path's accuracy contract)."""
     check(self._lib.ffn_engine_set_option(self._h, name.encode(), int(value)))
     if name == 'conv_variant' and explicit and int(value) != -1:
       self.variant_is_explicit = True
+
+  @property
+  def default_variant(self) -> int:
+    """The conv_variant the engine chose for its geometry when it was created."""
+    return self._default_variant
 
   def restore_default_variant(self):
     """Back to the kernel choice the engine was created with, as if nobody had

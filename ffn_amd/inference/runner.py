@@ -52,12 +52,22 @@ class Runner:
   #: (ffn_canvas_create_u8); False = normalise on the host as the reference does
   DEVICE_U8 = True
 
-  def __init__(self, device_id: int = 0, conv_variant: Optional[int] = None):
+  def __init__(self, device_id: int = 0, conv_variant: Optional[int] = None,
+               precision: str = 'f32'):
     """conv_variant: None = the engine's default (9: conv32mt for steps of one
     FoV; with batch_size > 1 the executor pins 8, conv32m, for every step); 2 =
     the exact-f32 kernel in the oracle's summation order (include/ffn_hip.h,
-    DESIGN.md section 3)."""
+    DESIGN.md section 3).
+
+    precision: 'f32' (default) or 'fp16' = engine option mfma_products 1: the
+    32 -> 32 convs of conv32m / conv32mt multiply fp16 operands once instead of
+    carrying every f32 product as three.  Faster batched steps, and OUTSIDE the
+    IoU >= 0.999 contract of the f32 path (DESIGN.md section 3.7 has the
+    numbers): an opt-in, as the reference's half-precision inference is."""
+    if precision not in ('f32', 'fp16'):
+      raise ValueError("precision must be 'f32' or 'fp16', got %r" % (precision,))
     self.conv_variant = conv_variant
+    self.precision = precision
     self.counters = inference_utils.Counters()
     self.executor = None
     self._exec_interface = executor.ExecutorInterface()
@@ -105,6 +115,16 @@ class Runner:
         batch_size, device_id=self.device_id)
     if self.conv_variant is not None:
       self.executor.engine.set_option('conv_variant', int(self.conv_variant))
+    if self.precision == 'fp16':
+      engine = self.executor.engine
+      # conv32m (8) / conv32mt (9) are the kernels with a one-product form; a
+      # geometry that admits them has one of the two as its default
+      if engine.default_variant not in (8, 9):
+        raise ValueError(
+            "precision='fp16' needs conv32m / conv32mt, which the FoV %s does not "
+            'admit (its default conv_variant is %d)' %
+            (engine.fov_zyx, engine.default_variant))
+      engine.set_option('mfma_products', 1)
     return model
 
   def start(self, request, batch_size: int = 1, session=None, direct=None,

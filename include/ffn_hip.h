@@ -442,6 +442,25 @@ int ffn_engine_set_pred_size(ffn_engine* engine, const int32_t pred_zyx[3]);
  *   reads 1; setting "flow" again re-arms).
  * "batch_chunks" 0..2 (variant 6): the form steps of several FoVs take;
  * "tail_batched" 1 = conv32mt for every step (one arithmetic whatever the batch).
+ * "mfma_products" 3 (default) or 1; anything else is FFN_ERR_ARG and stores nothing.
+ *   fp16 inference, opt-in: with 1 the 32 -> 32 convs of conv32m / conv32mt compute
+ *   sum hi(w) hi(a) in f32 accumulators -- hi() = the operand's fp16 half, i.e. the
+ *   f32 value rounded to nearest-even fp16 with |v| < 2^-14 becoming 0 -- and drop the
+ *   two cross products that make the default path f32-accurate (one MFMA instead of
+ *   three per operand pair, half the LDS fragment reads).  conv0_a, the head, bias, ReLU,
+ *   the residual add and the f32 residual stream, gather / faces / paste and the fp16
+ *   range guard are unchanged.  It takes effect where a stack runs conv32m or conv32mt
+ *   (conv_variant 8 and 9; batched steps of 6 with batch_chunks 2); every other kernel
+ *   family -- conv32, conv32c, conv32d in both chunk sizes, conv32h -- ignores it and
+ *   computes as always, which is what lets a range-voided step be repeated on the exact
+ *   kernel with the option stored.  The one-product kernels exist as per-layer launches
+ *   only: a single-FoV step runs conv32mt as under "flow" = 0, never the resident launch.
+ *   OUTSIDE the accuracy contract of the default path: the logits differ from f32 by
+ *   ~1e-3 .. 1e-2 per step (a thousand times the split kernels' distance), the FoV loop
+ *   amplifies that, and whole runs stand to the f32 run at foreground IoU 0.92 .. 0.9999
+ *   (250^3 volumes: 0.92 .. 0.93), not >= 0.999.  It pays for
+ *   batched steps (0.71 of the time per conv); a single FoV is 10 % slower with it.  Same trade as the reference's half-precision
+ *   inference: throughput for a slightly higher merge error rate; the user's choice.
  * "speculate" (default 1): single-FoV steps of the segment loop queue conv0_a of the
  *   NEXT step behind their paste, for the positions the loop expects to pop next; a
  *   step whose launch chose another position pastes nothing and is made again.

@@ -43,6 +43,10 @@ def main(argv=None):
                   'single-FoV steps / conv32m for batched ones; 8 = conv32m; 2 = '
                   'exact f32 in the oracle\'s summation order; 6 = conv32d, '
                   'K-split); see DESIGN.md section 3')
+  ap.add_argument('--precision', choices=['f32', 'fp16'], default='f32',
+                  help='fp16: one fp16 MFMA product per 32->32 conv instead of the '
+                  'f32-accurate three (engine option mfma_products 1). Faster batched '
+                  'steps; outside the IoU >= 0.999 contract, see DESIGN.md section 3.7')
   ap.add_argument('--assemble', default='',
                   help='With sharding: also assemble ONE global label volume '
                   '(RCCL all-reduce + union-find reconciliation of objects cut '
@@ -66,7 +70,8 @@ def main(argv=None):
   local_rank = int(os.environ.get('LOCAL_RANK', '0'))
   world = int(os.environ.get('WORLD_SIZE', '1'))
 
-  runner = runner_lib.Runner(device_id=local_rank, conv_variant=args.conv_variant)
+  runner = runner_lib.Runner(device_id=local_rank, conv_variant=args.conv_variant,
+                             precision=args.precision)
   runner.start(request, batch_size=args.batch_size,
                direct=True if args.assemble else None)
 
