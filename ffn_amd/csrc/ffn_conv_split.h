@@ -113,9 +113,73 @@ struct ConvDArgs {
                          // behind the poll; 4 buffer_wbl2 sc1 in front of the publish
 };
 
+// The production form of the resident stack (conv32ps_kernel<false>) takes these instead:
+// the same fields under the same names, without the lab's (dbg, layer; dbg_wgs,
+// flow_trace, flow_dbg), without the launch's own ConvLayer (the stack derives one per
+// conv) and without what only a plain launch's workgroup map reads (nchunks, total_slots,
+// slots_per_xcd, magic_nchunks, aoff: a tail workgroup's table is ConvTailMap::taoff).
+struct ConvLayerLean {
+  const char* in_sp;
+  char* out_sp;
+  const char* wpack;
+  const float* bias;
+  unsigned flow_wait;
+  unsigned flow_set;
+  int flow_wait_on;
+};
+
+struct ConvDArgsLean {
+  float* x_f32;
+  long item_bytes;
+  long sp_plane_bytes;
+  int XS, plane, V, fx, fyfx;
+  unsigned magic_fyfx, magic_fx;
+  int permuted;
+  int ds0, ds1, ds2;
+  unsigned sp_bytes;
+  int btap[4 * 8];
+  const float* head_w;
+  const float* seed_raw;
+  float* logits;
+  unsigned* head_count;
+  float pad_value, move_thr;
+  unsigned* range_flag;
+  unsigned range_tag;
+  unsigned* flow_flags;
+  int flow_n_main;
+  unsigned* flow_err;
+  int flow_halo;
+};
+
+inline ConvDArgsLean lean_args(const ConvDArgs& a) {
+  ConvDArgsLean q;
+  q.x_f32 = a.x_f32;
+  q.item_bytes = a.item_bytes;
+  q.sp_plane_bytes = a.sp_plane_bytes;
+  q.XS = a.XS, q.plane = a.plane, q.V = a.V, q.fx = a.fx, q.fyfx = a.fyfx;
+  q.magic_fyfx = a.magic_fyfx, q.magic_fx = a.magic_fx;
+  q.permuted = a.permuted;
+  q.ds0 = a.ds0, q.ds1 = a.ds1, q.ds2 = a.ds2;
+  q.sp_bytes = a.sp_bytes;
+  for (int i = 0; i < 4 * 8; ++i) q.btap[i] = a.btap[i];
+  q.head_w = a.head_w;
+  q.seed_raw = a.seed_raw;
+  q.logits = a.logits;
+  q.head_count = a.head_count;
+  q.pad_value = a.pad_value, q.move_thr = a.move_thr;
+  q.range_flag = a.range_flag;
+  q.range_tag = a.range_tag;
+  q.flow_flags = a.flow_flags;
+  q.flow_n_main = a.flow_n_main;
+  q.flow_err = a.flow_err;
+  q.flow_halo = a.flow_halo;
+  return q;
+}
+
 // dense index v of this layout -> index in the caller's dense [z][y][x] order
 // (logits, seed_raw); the identity unless the axes are permuted
-__device__ __forceinline__ int caller_index(const ConvDArgs& a, int v) {
+template <class A>
+__device__ __forceinline__ int caller_index(const A& a, int v) {
   if (!a.permuted) return v;
   const int z = (int)__umulhi((unsigned)v, a.magic_fyfx);
   const int rem = v - z * a.fyfx;
@@ -207,7 +271,29 @@ constexpr bool kPollMerged = FFN_POLL_MERGED != 0;
 // one, cost 10 - 25 % of the step).
 constexpr int kFlowStride = 64;  // words between two producers' words
 
-__device__ __forceinline__ int flow_unit(const ConvDArgs& a, int d) {
+// The lab's run-time plumbing (clock stamps, flow traces, the flow_debug bits) as the FLOW
+// bodies read it.  LAB = false is the production form of the resident stack
+// (conv32ps_kernel, ffn_conv_resident.h): its argument structs (ConvLayerLean,
+// ConvDArgsLean) do not have these fields, the answers are constants and everything that
+// hangs on them is compiled out.  LAB = true: the field reads they stand for.
+template <bool LAB, class LT>
+__device__ __forceinline__ long long* lab_dbg(const LT& L) {
+  if constexpr (LAB) return L.dbg;
+  else return nullptr;
+}
+template <bool LAB, class A>
+__device__ __forceinline__ bool lab_trace(const A& a) {
+  if constexpr (LAB) return FFN_FLOW_TRACE && a.flow_trace;
+  else return false;
+}
+template <bool LAB, class A>
+__device__ __forceinline__ int lab_flow_dbg(const A& a) {
+  if constexpr (LAB) return a.flow_dbg;
+  else return 0;
+}
+
+template <class A>
+__device__ __forceinline__ int flow_unit(const A& a, int d) {
   if (a.flow_n_main < 0)  // conv32h: uniform 80-voxel producers (d / 80)
     return (int)__umulhi((unsigned)d, 53687092u);
   const int m = a.flow_n_main * 128;  // (= kMChunk)
@@ -219,13 +305,14 @@ __device__ __forceinline__ int flow_unit(const ConvDArgs& a, int d) {
 // roughly in index order (the lower planes lead), so the wave first polls ONE
 // word, the last producer's -- one memory transaction per poll -- and then
 // looks at all of them once.
-__device__ __forceinline__ void flow_wait_tiles(const ConvDArgs& a, const ConvLayer& L,
+template <bool LAB = true, class A = ConvDArgs, class LT = ConvLayer>
+__device__ __forceinline__ void flow_wait_tiles(const A& a, const LT& L,
                                                 int d_lo, int d_hi, int lane) {
   typedef FFN_GLOBAL unsigned gu32;
   if (d_lo > a.V - 1 || d_hi < 0) return;
   int lo = flow_unit(a, d_lo < 0 ? 0 : d_lo);
   int hi = flow_unit(a, d_hi > a.V - 1 ? a.V - 1 : d_hi);
-  if (kExp && (a.flow_dbg & 1)) {
+  if (kExp && (lab_flow_dbg<LAB>(a) & 1)) {
     lo = 0;
     hi = flow_unit(a, a.V - 1);
   }
@@ -252,7 +339,7 @@ __device__ __forceinline__ void flow_wait_tiles(const ConvDArgs& a, const ConvLa
                a.range_tag;
   };
   auto nap = [&]() {
-    const int sl = kExp ? (a.flow_dbg >> 8) & 3 : 0;
+    const int sl = kExp ? (lab_flow_dbg<LAB>(a) >> 8) & 3 : 0;
     if (sl == 0) __builtin_amdgcn_s_sleep(8);
     else if (sl == 1) __builtin_amdgcn_s_sleep(2);
     else if (sl == 2) __builtin_amdgcn_s_sleep(16);
@@ -282,7 +369,7 @@ __device__ __forceinline__ void flow_wait_tiles(const ConvDArgs& a, const ConvLa
     }
     return;
   }
-  if (!(kExp && (a.flow_dbg & 64))) {
+  if (!(kExp && (lab_flow_dbg<LAB>(a) & 64))) {
     for (;;) {  // the last producer's word, every lane the same address
       const unsigned x = __hip_atomic_load(flags + (long)hi * kFlowStride, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
@@ -307,18 +394,21 @@ __device__ __forceinline__ void flow_wait_tiles(const ConvDArgs& a, const ConvLa
 
 // every wave of the workgroup, behind its last activation store: drain, meet,
 // then one lane publishes the workgroup's word (first dense voxel v0)
-__device__ __forceinline__ long long flow_publish(const ConvDArgs& a, const ConvLayer& L,
+template <bool LAB = true, class A = ConvDArgs, class LT = ConvLayer>
+__device__ __forceinline__ long long flow_publish(const A& a, const LT& L,
                                                   int v0, int tid) {
   typedef FFN_GLOBAL unsigned gu32;
   if constexpr (!(kAbl & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (kExp && (a.flow_dbg & 4))
+  if (kExp && (lab_flow_dbg<LAB>(a) & 4))
     asm volatile("buffer_wbl2 sc1\n\ts_waitcnt vmcnt(0)" ::: "memory");
-  const long long t_drained = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  const long long t_drained = lab_trace<LAB>(a) ? wall_clock64() : 0;
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   const int unit = flow_unit(a, v0);
   // (fault injection, flow_debug 2048: producer 3 stays silent after the first conv)
-  const bool silent = (a.flow_dbg & kFlowFaultBit) && unit == 3 && L.layer >= 1;
+  // (the production form has neither the bit nor the layer index)
+  bool silent = false;
+  if constexpr (LAB) silent = (a.flow_dbg & kFlowFaultBit) && unit == 3 && L.layer >= 1;
   if (tid == 0 && !silent)
     __hip_atomic_store((gu32*)a.flow_flags + (long)unit * kFlowStride,
                        L.flow_set, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -426,8 +516,9 @@ __device__ __forceinline__ void split8_fp16(const f32x4& v0, const f32x4& v1,
 // queue are PROD = 3's (the residual weight fragments are still fetched and
 // waited for where their MFMA stood), so every hand-placed vmcnt holds as it is.
 template <int KIND, bool ADD_SKIP, int KS, bool HEAD, int NT, int R, int WPS,
-          bool FLOW = false, int PROD = 3>
-__device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer& L,
+          bool FLOW = false, int PROD = 3, bool LAB = true, class A = ConvDArgs,
+          class LT = ConvLayer>
+__device__ __forceinline__ void conv32d_body(const A& a, const LT& L,
                                              const int item,
                                              const int v0, const int gc,
                                              const int* aoff_tab, const bool dbg_here) {
@@ -443,10 +534,10 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
   extern __shared__ __attribute__((aligned(16))) float lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
   const int tid = threadIdx.x;
-  const long long dbg_c0 = L.dbg ? clock64() : 0;
-  const long long dbg_w0 = L.dbg ? wall_clock64() : 0;
+  const long long dbg_c0 = lab_dbg<LAB>(L) ? clock64() : 0;
+  const long long dbg_w0 = lab_dbg<LAB>(L) ? wall_clock64() : 0;
   long long ft[6] = {0, 0, 0, 0, 0, 0};
-  if constexpr (FLOW) ft[0] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  if constexpr (FLOW) ft[0] = lab_trace<LAB>(a) ? wall_clock64() : 0;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int aoffs[7], btaps[7];
 #pragma unroll
@@ -527,11 +618,11 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
     hiddenW(btaps[3], W3);
     if (L.flow_wait_on) {
       if (wave == 0)
-        flow_wait_tiles(a, L, v0 - a.flow_halo, v0 + kChunkD - 1 + a.flow_halo, lane);
-      ft[1] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+        flow_wait_tiles<LAB>(a, L, v0 - a.flow_halo, v0 + kChunkD - 1 + a.flow_halo, lane);
+      ft[1] = lab_trace<LAB>(a) ? wall_clock64() : 0;
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (kExp && (a.flow_dbg & 2)) asm volatile("buffer_inv sc1" ::: "memory");
+      if (kExp && (lab_flow_dbg<LAB>(a) & 2)) asm volatile("buffer_inv sc1" ::: "memory");
     }
 #pragma unroll
     for (int seg = 0; seg < 3; ++seg)
@@ -606,8 +697,8 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   pinW(W0);
-  const long long dbg_c1 = L.dbg ? clock64() : 0;
-  if constexpr (FLOW) ft[2] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  const long long dbg_c1 = lab_dbg<LAB>(L) ? clock64() : 0;
+  if constexpr (FLOW) ft[2] = lab_trace<LAB>(a) ? wall_clock64() : 0;
   loadX(0, aoffs[0], X0);
 
   // EXTRA: memory instructions riding on the tile (issued behind its prefetch)
@@ -735,8 +826,8 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
 #undef FFN_DTAP
 #undef FFN_DTILE
 
-  const long long dbg_c2 = L.dbg ? clock64() : 0;
-  if constexpr (FLOW) ft[3] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  const long long dbg_c2 = lab_dbg<LAB>(L) ? clock64() : 0;
+  if constexpr (FLOW) ft[3] = lab_trace<LAB>(a) ? wall_clock64() : 0;
   // ---- epilogue: the four waves' partial sums meet in LDS ----
   // P[wave][position 0..159][32 ch] at a 144-B row stride; accumulator register
   // 4 g + i of a lane is channel 8 g + 4 (lane >> 5) + i of position lane & 31.
@@ -859,20 +950,22 @@ __device__ __forceinline__ void conv32d_body(const ConvDArgs& a, const ConvLayer
     // host re-runs it with the exact-f32 kernel (ffn_step_result.range_error)
     if (!(FLOW && kAbl) && __ballot(range_max > 0x477fe000u) && lane == 0)  // > 65504 (or NaN)
       *a.range_flag = a.range_tag;
-    if constexpr (FLOW) ft[4] = flow_publish(a, L, v0, tid);
+    if constexpr (FLOW) ft[4] = flow_publish<LAB>(a, L, v0, tid);
   }
   if constexpr (FLOW) {
-    ft[5] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
-    flow_trace_row(a, L, gc, ft);
+    ft[5] = lab_trace<LAB>(a) ? wall_clock64() : 0;
+    if constexpr (LAB) flow_trace_row(a, L, gc, ft);
   }
-  if (L.dbg && dbg_here && (tid & 63) == 0) {
-    long long* d = L.dbg + wave * 6;
-    d[0] = dbg_c0;
-    d[1] = dbg_c1;
-    d[2] = dbg_c2;
-    d[3] = clock64();
-    d[4] = dbg_w0;
-    d[5] = wall_clock64();
+  if constexpr (LAB) {
+    if (L.dbg && dbg_here && (tid & 63) == 0) {
+      long long* d = L.dbg + wave * 6;
+      d[0] = dbg_c0;
+      d[1] = dbg_c1;
+      d[2] = dbg_c2;
+      d[3] = clock64();
+      d[4] = dbg_w0;
+      d[5] = wall_clock64();
+    }
   }
 }
 
@@ -982,8 +1075,8 @@ __device__ __forceinline__ f32x4 hidden_load16f(const char* sbase, unsigned voff
 // takes `acc` as it is.  Staging, the weight ring, m_wait and the barriers are
 // PROD = 3's: all eight planes and the 4-KB taps are still copied.
 template <int KIND, bool ADD_SKIP, bool HEAD, bool FLOW = false, bool RES = false,
-          int PROD = 3>
-__device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer& L,
+          int PROD = 3, bool LAB = true, class A = ConvDArgs, class LT = ConvLayer>
+__device__ __forceinline__ void conv32m_body(const A& a, const LT& L,
                                              const int item,
                                              const int v0, const int gc,
                                              const bool dbg_here,
@@ -1000,10 +1093,10 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
   extern __shared__ __attribute__((aligned(16))) float lds[];
   char* ldsb = reinterpret_cast<char*>(lds);
   const int tid = threadIdx.x;
-  const long long dbg_c0 = L.dbg ? clock64() : 0;
-  const long long dbg_w0 = L.dbg ? wall_clock64() : 0;
+  const long long dbg_c0 = lab_dbg<LAB>(L) ? clock64() : 0;
+  const long long dbg_w0 = lab_dbg<LAB>(L) ? wall_clock64() : 0;
   long long ft[6] = {0, 0, 0, 0, 0, 0};
-  if constexpr (FLOW) ft[0] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  if constexpr (FLOW) ft[0] = lab_trace<LAB>(a) ? wall_clock64() : 0;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   auto padded = [&](int v) {
     v = v < a.V ? v : a.V - 1;
@@ -1053,14 +1146,14 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
       // the rows of dz = -1 and dz = 0; those of dz = +1 are not needed before
       // tap 9 queues their DMA: their words are fetched during tap 1 (below)
       if (wave == 0)
-        flow_wait_tiles(a, L, v0 - a.flow_halo,
-                        (kExp && (a.flow_dbg & 32)) ? v0 + kMChunk - 1 + a.flow_halo
+        flow_wait_tiles<LAB>(a, L, v0 - a.flow_halo,
+                        (kExp && (lab_flow_dbg<LAB>(a) & 32)) ? v0 + kMChunk - 1 + a.flow_halo
                                                     : v0 + kMChunk - 1 + a.fx + 1,
                         lane);
-      ft[1] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+      ft[1] = lab_trace<LAB>(a) ? wall_clock64() : 0;
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (kExp && (a.flow_dbg & 2)) asm volatile("buffer_inv sc1" ::: "memory");
+      if (kExp && (lab_flow_dbg<LAB>(a) & 2)) asm volatile("buffer_inv sc1" ::: "memory");
     }
   }
   dma_seg(0);
@@ -1107,8 +1200,8 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
   wait_vmcnt<kMPieces>();  // W0 .. W(D-2), dz = -1 landed
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  const long long dbg_c1 = L.dbg ? clock64() : 0;
-  if constexpr (FLOW) ft[2] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  const long long dbg_c1 = lab_dbg<LAB>(L) ? clock64() : 0;
+  if constexpr (FLOW) ft[2] = lab_trace<LAB>(a) ? wall_clock64() : 0;
   dma_w(D - 1);
   load_w(0, 0, W0);
   load_w(0, 1, W0);
@@ -1143,7 +1236,7 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
   unsigned late_word = 0;
   const int late_d_lo = v0 + a.fyfx - a.fx - 1;
   const bool late_on =
-      FLOW && L.flow_wait_on && !(kExp && (a.flow_dbg & 32)) && late_d_lo <= a.V - 1;
+      FLOW && L.flow_wait_on && !(kExp && (lab_flow_dbg<LAB>(a) & 32)) && late_d_lo <= a.V - 1;
   auto flow_late_load = [&]() {
     if constexpr (FLOW) {
       const int lo = flow_unit(
@@ -1167,7 +1260,7 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
     if constexpr (FLOW) {
       asm volatile("" : "+v"(late_word));
       if (late_on && wave == 0 && !__all((int)(late_word - L.flow_wait) >= 0))
-        flow_wait_tiles(a, L, late_d_lo, v0 + kMChunk - 1 + a.flow_halo, lane);
+        flow_wait_tiles<LAB>(a, L, late_d_lo, v0 + kMChunk - 1 + a.flow_halo, lane);
     }
   };
 #define FFN_MGAP(S, PART, WNEXT, XNEXT)                                         \
@@ -1273,8 +1366,12 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
   FFN_MTAP(26, X2, W0, W1, X1)
 #undef FFN_MTAP
 #undef FFN_MGAP
-  const long long dbg_c2 = L.dbg ? clock64() : 0;
-  if constexpr (FLOW) ft[3] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
+  // (the production form: without the clock stamps' branches around the taps nothing else
+  // keeps the MFMAs of taps 9 .. 26 from being sunk behind the last barrier, next to the
+  // epilogue that reads their sums)
+  if constexpr (!LAB) asm volatile("" : "+a"(acc), "+a"(accC));
+  const long long dbg_c2 = lab_dbg<LAB>(L) ? clock64() : 0;
+  if constexpr (FLOW) ft[3] = lab_trace<LAB>(a) ? wall_clock64() : 0;
 
   // ---- epilogue: straight from the accumulators (lane = position jpos,
   // register 4 g + i = channel 8 g + 4 lh + i) ----
@@ -1373,20 +1470,22 @@ __device__ __forceinline__ void conv32m_body(const ConvDArgs& a, const ConvLayer
     }
     if (!(FLOW && kAbl) && __ballot(range_max > 0x477fe000u) && lane == 0)  // > 65504 (or NaN)
       *a.range_flag = a.range_tag;
-    if constexpr (FLOW) ft[4] = flow_publish(a, L, v0, tid);
+    if constexpr (FLOW) ft[4] = flow_publish<LAB>(a, L, v0, tid);
   }
   if constexpr (FLOW) {
-    ft[5] = (FFN_FLOW_TRACE && a.flow_trace) ? wall_clock64() : 0;
-    flow_trace_row(a, L, gc, ft);
+    ft[5] = lab_trace<LAB>(a) ? wall_clock64() : 0;
+    if constexpr (LAB) flow_trace_row(a, L, gc, ft);
   }
-  if (L.dbg && dbg_here && lane == 0) {
-    long long* d = L.dbg + wave * 6;
-    d[0] = dbg_c0;
-    d[1] = dbg_c1;
-    d[2] = dbg_c2;
-    d[3] = clock64();
-    d[4] = dbg_w0;
-    d[5] = wall_clock64();
+  if constexpr (LAB) {
+    if (L.dbg && dbg_here && lane == 0) {
+      long long* d = L.dbg + wave * 6;
+      d[0] = dbg_c0;
+      d[1] = dbg_c1;
+      d[2] = dbg_c2;
+      d[3] = clock64();
+      d[4] = dbg_w0;
+      d[5] = wall_clock64();
+    }
   }
 }
 

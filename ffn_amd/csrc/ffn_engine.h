@@ -43,6 +43,8 @@ __attribute__((format(printf, 2, 3))) inline int fail(int code, const char* fmt,
                   hipGetErrorString(_e), __FILE__, __LINE__);                \
   } while (0)
 
+constexpr int kDbgLayerDefault = 3;  // engine option debug_layer as an engine starts
+
 struct ffn_engine {
   // Entry points may be called from several host threads (the two canvas groups
   // of MultiCanvasDriver, their between-segment work): each one holds this lock
@@ -95,7 +97,7 @@ struct ffn_engine {
   int store_policy = 1;  // conv32c epilogue stores: sc1 write-through (-1.4 % per stack)
   long long* d_dbg = nullptr;  // debug clocks of conv32c WG 0 (24 values)
   int dbg_clock = 0;
-  int dbg_layer = 3;      // the launch whose clocks are recorded (3 = a conv_a)
+  int dbg_layer = kDbgLayerDefault;  // the launch whose clocks are recorded (3 = a conv_a)
   // rawT / rawX / rawS: the three activation allocations
   float* rawT = nullptr;
   float* rawX = nullptr;
@@ -113,6 +115,12 @@ struct ffn_engine {
   unsigned* flow_err = nullptr;    // polls that gave up, ever
   unsigned flow_epoch = 0;         // sequence number of the last conv queued
   int flow_debug = 0;              // debug option: ConvDArgs::flow_dbg
+  // The resident stack and the fused step launch exist twice: the production form, and the
+  // LAB form that carries the lab's plumbing (debug_clock, debug_layer, flow_debug,
+  // debug_fused_trace, the flow trace).  flow_lab 0: the LAB form where one of those is on
+  // (lab_wanted, ffn_hip.hip); 1: always.
+  int flow_lab = 0;
+  long stat_lab_launches = 0;      // resident stacks queued in the LAB form
   // The resident launch needs every one of its workgroups on the chip at once.
   // flow_fits: the device can hold them (CU count x occupancy, checked at create);
   // at run time a poll that gives up voids the step (FFN_ERR_FLOW): the repeat

@@ -161,7 +161,8 @@ int set_lds_attr_m() {
 #undef FFN_H
 #undef FFN_M1
   FFN_LDS_ATTR(conv32hs_kernel, kHLdsBytes);
-  FFN_LDS_ATTR(conv32ps_kernel, kMLdsBytes);
+  FFN_LDS_ATTR(conv32ps_kernel<true>, kMLdsBytes);
+  FFN_LDS_ATTR(conv32ps_kernel<false>, kMLdsBytes);
   return FFN_OK;
 }
 
@@ -541,6 +542,15 @@ void stack_tab(ffn_engine* e, const uint16_t* wpack, int auto_pace, ConvStackTab
   tb->trace = 0;
 }
 
+// Whether the launches of a step take their LAB form: one of the lab's run-time options is
+// on (the production forms have no code for them), the build is an experiment or ablation
+// build, or engine option flow_lab asks for it.  (debug_fused_trace is per launch: a
+// launch that stamps is a LAB launch, launch_conv32ps and the fused step launch.)
+bool lab_wanted(const ffn_engine* e) {
+  return e->flow_lab != 0 || kExp || kAbl != 0 || FFN_FLOW_TRACE != 0 || e->dbg_clock != 0 ||
+         e->dbg_layer != kDbgLayerDefault || e->flow_debug != 0;
+}
+
 // The 2 depth - 1 convs of ONE FoV as a single resident launch (conv32ps,
 // ffn_conv_resident.h): conv32mt's workgroups keep their voxels through the stack and
 // hand rows to each other through the tile words instead of kernel boundaries.
@@ -565,11 +575,22 @@ int launch_conv32ps(ffn_engine* e, const StackPlan& plan, float pad_value, float
   // (2: the stack in front of the traced step, queued ahead one call earlier: its end only)
   tb.trace = e->trace_now ? 1 : (ahead_choice && e->fused_trace_in == 1) ? 2 : 0;
   const long long t_l0 = e->t_arrived_ns ? steady_ns() : 0;
-  if (ev0)
-    hipExtLaunchKernelGGL(conv32ps_kernel, grid, block, kMLdsBytes, e->stream, ev0, ev1, 0, a,
-                          mp, tb);
-  else
-    hipLaunchKernelGGL(conv32ps_kernel, grid, block, kMLdsBytes, e->stream, a, mp, tb);
+  if (lab_wanted(e) || tb.trace != 0) {
+    e->stat_lab_launches += 1;
+    if (ev0)
+      hipExtLaunchKernelGGL(conv32ps_kernel<true>, grid, block, kMLdsBytes, e->stream, ev0, ev1,
+                            0, a, mp, tb);
+    else
+      hipLaunchKernelGGL(conv32ps_kernel<true>, grid, block, kMLdsBytes, e->stream, a, mp, tb);
+  } else {
+    const ConvDArgsLean al = lean_args(a);
+    const ConvStackTabLean tl = lean_tab(tb);
+    if (ev0)
+      hipExtLaunchKernelGGL(conv32ps_kernel<false>, grid, block, kMLdsBytes, e->stream, ev0, ev1,
+                            0, al, mp, tl);
+    else
+      hipLaunchKernelGGL(conv32ps_kernel<false>, grid, block, kMLdsBytes, e->stream, al, mp, tl);
+  }
   if (e->t_arrived_ns) {
     const long long t_l1 = steady_ns();
     if (t_l1 - e->t_arrived_ns < 100000) {  // (inside a segment: see ConvStackTab::stamps)
@@ -967,11 +988,17 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
     // where the device can hold all of its workgroups at once: they wait for
     // each other, so one that is not on the chip stalls the rest until their
     // polls give up (a partitioned device, fewer CUs than main chunks)
-    int per_cu = 0;
-    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel),
+    // (both forms of the kernel: the smaller occupancy decides)
+    int per_cu = 0, per_cu_lab = 0;
+    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
-    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32ps_kernel,
+    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32ps_kernel<false>,
                                                        kDThreads, kMLdsBytes));
+    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel<true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
+    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_lab, conv32ps_kernel<true>,
+                                                       kDThreads, kMLdsBytes));
+    per_cu = std::min(per_cu, per_cu_lab);
     ConvTailMap mp;
     tail_map(e, 1, mp);
     const int grid = 8 * (mp.mains_per_xcd + mp.tails_per_xcd);
@@ -1609,12 +1636,17 @@ int ffn_canvas_step_submit(ffn_engine* e, int n, ffn_canvas* const* canvases,
         ? e->paste_blocks
         : std::max(kPasteBlocksMin, std::min(kPasteBlocks, e->cus - 1 - tiles));
     const auto fused = [&](int trace) {
-      hipLaunchKernelGGL(faces_paste_conv0a_kernel, dim3(1 + paste_blocks + tiles),
-                         dim3(512), 0, e->stream, si, g, e->logits, e->seed_raw, e->count,
-                         e->count_blocks, params->move_threshold,
-                         params->disco_seed_threshold, params->deleted_threshold,
-                         e->range_flag, e->range_tag, h_pub, step_id, e->d_spec_choice,
-                         spec_expected, nx, e->d_stamps, trace, paste_blocks);
+#define FFN_FUSED(LABV)                                                                    \
+  hipLaunchKernelGGL(faces_paste_conv0a_kernel<LABV>, dim3(1 + paste_blocks + tiles),      \
+                     dim3(512), 0, e->stream, si, g, e->logits, e->seed_raw, e->count,     \
+                     e->count_blocks, params->move_threshold,                              \
+                     params->disco_seed_threshold, params->deleted_threshold,              \
+                     e->range_flag, e->range_tag, h_pub, step_id, e->d_spec_choice,        \
+                     spec_expected, nx, e->d_stamps, trace, paste_blocks)
+      // (the production form does not stamp: a traced launch, or flow_lab, takes the other)
+      if (trace != 0 || e->flow_lab != 0) FFN_FUSED(true);
+      else FFN_FUSED(false);
+#undef FFN_FUSED
     };
     // (experiment debug_fused_twice: the same launch made twice -- idempotent: same record,
     // same paste, same conv0_a -- so that the second, traced one starts on warm caches)

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "ffn_types.h"
 
 namespace ffn {
@@ -28,12 +30,30 @@ __device__ __forceinline__ bool in_pred_box(const Geom& g, int z, int y, int x) 
          x < g.c1[2];
 }
 
+// Bytes of the explicit kernel arguments of a kernel with parameters of types T...: each
+// at its natural alignment, in order (the layout of the kernarg segment); or of the kernel
+// a function pointer type names.
+template <class... T>
+constexpr int kernarg_bytes() {
+  size_t off = 0;
+  ((off = (off + alignof(T) - 1) / alignof(T) * alignof(T) + sizeof(T)), ...);
+  return (int)off;
+}
+template <class F>
+struct KernargsOf;
+template <class... T>
+struct KernargsOf<void (*)(T...)> {
+  static constexpr int bytes = kernarg_bytes<T...>();
+};
+
 // The kernel arguments of a launch that has just crossed a boundary are cold (the scalar
 // cache was invalidated, the host wrote them to device memory), and a kernel with roles and
 // branches reads them in STAGES: every s_load behind a branch is its own miss, 0.5 - 1 us
 // each, one behind the other (the fused step launch: six stages before its first data load).
 // This touches every 64-byte line of the first BYTES of the segment at once and waits for
 // them once: one miss, the stages after it hit the scalar cache.
+// BYTES comes from the kernel's own parameter types (kernarg_bytes below): a read past
+// the explicit arguments is a read of whatever follows the segment.
 template <int BYTES>
 __device__ __forceinline__ void warm_kernargs() {
   const auto ka = __builtin_amdgcn_kernarg_segment_ptr();

@@ -100,6 +100,7 @@ int set_stat_reset(ffn_engine* e, int) {
   std::memset(e->stat_hist, 0, sizeof(e->stat_hist));
   e->stat_turn_host_ns = e->stat_launch_host_ns = 0;
   e->stat_turn_host_count = 0;
+  e->stat_lab_launches = 0;
   e->t_arrived_ns = 0;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -236,6 +237,7 @@ const Option kOptions[] = {
     derived("flow_pace_now", FFN_GET(e->flow_pace < 0 ? e->pace_auto : e->flow_pace)),
     derived("flow_pace_free_ns", FFN_GET((int)(e->pace_auto_us[0] * 1e3f))),
     derived("flow_pace_best_ns", FFN_GET((int)(e->pace_auto_us[1] * 1e3f))),
+    {"flow_lab", &E::flow_lab, 0, 1},
     {"flow_debug", &E::flow_debug},
     {"debug_clock", &E::dbg_clock},
     {"debug_layer", &E::dbg_layer},
@@ -261,6 +263,7 @@ const Option kOptions[] = {
     counter("stat_many_carried", &E::stat_many_carried),
     counter("stat_flow_voids", &E::stat_flow_voids),
     derived("stat_flow_timeouts", get_stat_flow_timeouts),
+    counter("stat_lab_launches", &E::stat_lab_launches),
     counter("stat_segturn_calls", &E::stat_segturn_calls),
     derived("stat_segturn_queue_ns",
             FFN_GET(mean_ns(e->stat_segturn_queue_ns, e->stat_segturn_calls))),

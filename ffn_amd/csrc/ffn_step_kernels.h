@@ -918,6 +918,11 @@ struct Conv0Next {
   SpecArgs sp;       // (choice: the next step's)
 };
 
+// LAB = false, the production form: without the debug_fused_trace stamps (`trace` is not
+// read, no role stamps, no stamps pointer into the faces and conv0_a bodies); the faces
+// block still leaves stamps[0] for stat_turn_gpu_ns.  The host picks (engine option
+// flow_lab, or a trace that is armed).
+template <bool LAB>
 __global__ __launch_bounds__(512) void faces_paste_conv0a_kernel(
     StepItems si, Geom g, const float* __restrict__ logits,
     const float* __restrict__ in_seed,
@@ -927,13 +932,19 @@ __global__ __launch_bounds__(512) void faces_paste_conv0a_kernel(
     const int* __restrict__ spec_choice, int spec_expected, Conv0Next nx,
     long long* __restrict__ stamps, int trace, int paste_blocks) {
   static_assert(kC0Threads == 512, "one block size for the three roles");
-  const long long t_in = wall_clock64();
-  warm_kernargs<832>();
-  const long long t_warm = wall_clock64();
+  long long t_in = 0, t_warm = 0;
+  if constexpr (LAB) t_in = wall_clock64();
+  // (every line of the explicit arguments, and none behind them)
+  constexpr int kArgBytes = KernargsOf<decltype(&faces_paste_conv0a_kernel<LAB>)>::bytes;
+  static_assert(kArgBytes >= (int)(sizeof(StepItems) + sizeof(Geom) + sizeof(Conv0Next)) &&
+                    kArgBytes <= 1024,
+                "the explicit arguments: all of them, within what warm_kernargs touches");
+  warm_kernargs<kArgBytes>();
+  if constexpr (LAB) t_warm = wall_clock64();
   // engine option debug_fused_trace (trace != 0): when each role of this launch ran --
   // first entry (min over the blocks) [4] faces, [5] paste, [6] conv0_a; last end (max) [8]
   // faces = record published, [9] paste, [10] conv0_a; ([7], [11]: the stack before it)
-  const bool tr_on = stamps && trace != 0;
+  const bool tr_on = LAB && stamps && trace != 0;
   struct RoleStamp {
     long long* lo;
     long long* hi;

@@ -34,6 +34,15 @@ extern "C" {
  * "ablate" (variant 2): issue-rate experiments of the conv_b launch (8, 16, 24).
  * "flow_debug" 2048: fault injection for tests (a producer stops publishing); its
  *   other bits and "debug_clock" 4 act only in -DFFN_EXPERIMENTS=1 builds.
+ * "flow_lab" 0 / 1: the resident stack (conv32ps_kernel) and the fused step launch
+ *   (faces_paste_conv0a_kernel) are built twice -- a production form without any of
+ *   the run-time plumbing of this header, and a LAB form with all of it.  0
+ *   (default): the LAB form runs where one of "debug_clock", "debug_layer",
+ *   "flow_debug" is away from its default, for a step traced by
+ *   "debug_fused_trace", and in -DFFN_EXPERIMENTS / -DFFN_ABLATE builds; the
+ *   production form otherwise.  1: always the LAB form.  Same results bit for bit.
+ *   "stat_lab_launches" (read-only, zeroed by "stat_reset"): resident stacks queued
+ *   in the LAB form.
  * "spec_force_mismatch" N: the next N steps that match a launch made ahead are
  *   treated as mismatches (test hook of the repeat path).
  * "debug_submit_delay_ns": the host idles this long in front of every step's
