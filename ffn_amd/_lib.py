@@ -153,6 +153,53 @@ class TurnResult(ctypes.Structure):
               ('chosen', ctypes.c_int32)]
 
 
+#: ffn_seed_record.outcome
+SEED_NO_STEPS, SEED_WEAK, SEED_TOO_SMALL, SEED_COMMITTED = 0, 1, 2, 3
+
+
+class SeedRecord(ctypes.Structure):
+  """ffn_seed_record (include/ffn_hip.h)."""
+  _fields_ = [('pos', ctypes.c_int32 * 3), ('outcome', ctypes.c_int32),
+              ('segment_id', ctypes.c_int32), ('num_overlaps', ctypes.c_int32),
+              ('first_overlap', ctypes.c_int64),
+              ('raw_segmented_voxels', ctypes.c_int64),
+              ('actual_segmented_voxels', ctypes.c_int64),
+              ('seconds', ctypes.c_double), ('segment', SegmentResult)]
+
+
+class SeedLoopArgs(ctypes.Structure):
+  """ffn_seed_loop_args (include/ffn_hip.h)."""
+  _fields_ = [('seeds', ctypes.c_void_p), ('num_seeds', ctypes.c_int64),
+              ('first_seed', ctypes.c_int64), ('segment', SegmentParams),
+              ('min_boundary_dist', ctypes.c_int32 * 3),
+              ('init_value', ctypes.c_float),
+              ('segment_threshold', ctypes.c_float),
+              ('half_pred', ctypes.c_int32 * 3),
+              ('min_segment_size', ctypes.c_int64),
+              ('next_segment_id', ctypes.c_int32),
+              ('max_existing_id', ctypes.c_int32),
+              ('turn_candidates', ctypes.c_int32), ('resume', ctypes.c_int32),
+              ('max_segments', ctypes.c_int32), ('has_deadline', ctypes.c_int32),
+              ('max_ms', ctypes.c_double), ('deadline_s', ctypes.c_double),
+              ('max_records', ctypes.c_int32), ('reserved', ctypes.c_int32),
+              ('records', ctypes.c_void_p), ('max_overlaps', ctypes.c_int64),
+              ('overlap_ids', ctypes.c_void_p),
+              ('overlap_counts', ctypes.c_void_p)]
+
+
+class SeedLoopResult(ctypes.Structure):
+  """ffn_seed_loop_result (include/ffn_hip.h)."""
+  _fields_ = [('next_seed', ctypes.c_int64), ('num_overlaps', ctypes.c_int64),
+              ('rejected_invalid', ctypes.c_int64),
+              ('rejected_segmented', ctypes.c_int64),
+              ('rejected_restricted', ctypes.c_int64),
+              ('rejected_too_close', ctypes.c_int64),
+              ('restricted_skips', ctypes.c_int64),
+              ('seconds', ctypes.c_double), ('num_records', ctypes.c_int32),
+              ('turns', ctypes.c_int32), ('exhausted', ctypes.c_int32),
+              ('in_segment', ctypes.c_int32)]
+
+
 class PairDesc(ctypes.Structure):
   """ffn_pair_desc (include/ffn_analysis.h)."""
   _fields_ = [('probs', ctypes.c_void_p), ('seg', ctypes.c_void_p),
@@ -243,6 +290,8 @@ SIGNATURES = {
                                   ctypes.POINTER(StepResult)]),
     'ffn_canvas_segment_at': (_I, [_P, _I3, ctypes.POINTER(SegmentParams), _I,
                                    ctypes.POINTER(SegmentResult)]),
+    'ffn_canvas_segment_all': (_I, [_P, ctypes.POINTER(SeedLoopArgs),
+                                    ctypes.POINTER(SeedLoopResult)]),
     'ffn_canvas_segment_many': (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     'ffn_canvas_segment_many_carry': (_I, [_P, _I, _P, _P, _P, _P, _P, _P,
                                            ctypes.c_int32]),

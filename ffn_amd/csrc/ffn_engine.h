@@ -291,6 +291,7 @@ struct ffn_canvas {
   int dirty_lo[3] = {0, 0, 0};
   int dirty_hi[3] = {0, 0, 0};  // exclusive; lo >= hi: nothing dirty
   ffn_host::SegmentState loop;  // ffn_canvas_segment_at's queue / visited set
+  ffn_host::SeedLoopState seed_loop;  // ffn_canvas_segment_all's interrupted segment
   hipEvent_t ev_util = nullptr;  // behind the last utility operation on this canvas
   bool util_pending = false;     // ... which the next step has to wait for
   bool paste_after_flag = false; // the last step pasted AFTER raising its flag

@@ -1880,6 +1880,12 @@ struct HipLoopDevice {
   int read_point(const int32_t pos[3], float* seed, int32_t* seg) {
     return ffn_canvas_read_points(c, 1, pos, seed, seg);
   }
+  int turn(const ffn_turn_request& rq, const int32_t* cand, ffn_turn_result* out,
+           int32_t max_overlaps, int32_t* ids, int64_t* counts, int32_t* flags,
+           float* cand_seed, int32_t* cand_seg) {
+    return ffn_canvas_segment_turn(c, &rq, cand, out, max_overlaps, ids, counts, flags,
+                                   cand_seed, cand_seg);
+  }
   // the positions the loop expects to pop after the step it is about to make
   void hint_next(int n, const int32_t (*pos)[3]) {
     EngineLock lock_(c->engine);
@@ -1930,6 +1936,21 @@ int ffn_canvas_segment_at(ffn_canvas* c, const int32_t start[3],
   HipLoopDevice dev{c};
   ffn_host::SegmentLoop<HipLoopDevice> loop(dev, c->loop, *p);
   return loop.run(start, resume, out);
+}
+
+int ffn_canvas_segment_all(ffn_canvas* c, const ffn_seed_loop_args* a,
+                           ffn_seed_loop_result* out) {
+  if (!c || !a || !out) return fail(FFN_ERR_ARG, "null argument");
+  if (!c->engine) return fail(FFN_ERR_STATE, "canvas outlived its engine");
+  if (!ffn_host::seed_loop_args_ok(*a))
+    return fail(FFN_ERR_ARG, "seed list, candidates, records or overlap arrays");
+  if (int rc = resolve_many_carry(c->engine, c)) return rc;
+  if (int rc = check_segment_params(c, a->segment, 0, -1)) return rc;
+  if (a->resume && !(c->seed_loop.in_segment && c->loop.active))
+    return fail(FFN_ERR_STATE, "no segment to resume");
+  HipLoopDevice dev{c};
+  ffn_host::SeedLoop<HipLoopDevice> loop(dev, c->loop, c->seed_loop, *a, out);
+  return loop.run();
 }
 
 int ffn_canvas_segment_many(ffn_engine* e, int n, ffn_canvas* const* canvases,

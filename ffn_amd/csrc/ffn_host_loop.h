@@ -13,13 +13,17 @@
 // Pure C++17, no HIP: the device is a template parameter with
 //   int step(const ffn_step_request&, const ffn_step_params&, ffn_step_result*)
 //   int read_point(const int32_t pos[3], float* seed, int32_t* seg)
-// (FFN_OK or an error code that is passed through).  libffn_hip.so instantiates
+// (FFN_OK or an error code that is passed through); the seed loop around it
+// (SeedLoop, below) also asks the device for the between-segment turn.
+// libffn_hip.so instantiates
 // it with the HIP canvas; tests/host_loop_shim.cpp with callbacks into the
 // emulated device, so the loop itself is covered without a GPU.
 #pragma once
 
 #include <cstdlib>
 #include <algorithm>
+#include <chrono>
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <deque>
@@ -493,6 +497,234 @@ class SegmentLoop {
   int32_t d_[3], dh_[3], dm_[3];
   int64_t steps_ = 0;
 };
+
+// What the seed loop keeps in the canvas between calls: the record of a segment
+// that an error interrupted (ffn_canvas_segment_all with resume = 1 finishes it).
+struct SeedLoopState {
+  bool in_segment = false;
+  ffn_seed_record rec{};
+};
+
+// Canvas.segment_all's seed loop (reference inference.py:573-660) without an
+// interpreter between two segments: the sequence DeviceCanvas drives through
+// _turn, _segment_at_native and _commit -- one turn answers the validity,
+// restrictor and too-close questions for the next seeds of the list and
+// initialises the first that passes, the segment loop runs from it, the weak-seed
+// test and the commit box follow, and the next turn commits or marks while it
+// tests the seeds after it.  Same decisions, same device calls, same order.  The
+// device also provides the turn:
+//   int turn(const ffn_turn_request&, const int32_t* cand, ffn_turn_result*,
+//            int32_t max_overlaps, int32_t* ids, int64_t* counts, int32_t* flags,
+//            float* cand_seed, int32_t* cand_seg)          (ffn_canvas_segment_turn)
+// A call returns between two seeds (include/ffn_hip.h): its last turn carries no
+// candidates, so nothing is initialised or tested ahead of what the caller is told.
+template <class Dev>
+class SeedLoop {
+ public:
+  SeedLoop(Dev& dev, SegmentState& st, SeedLoopState& sl, const ffn_seed_loop_args& a,
+           ffn_seed_loop_result* out)
+      : dev_(dev), st_(st), sl_(sl), a_(a), out_(out) {}
+
+  int run() {
+    std::memset(out_, 0, sizeof(*out_));
+    t0_ = Clock::now();
+    idx_ = a_.first_seed;
+    next_id_ = a_.next_segment_id;
+    max_id_ = a_.max_existing_id;
+    const int cap = a_.turn_candidates;
+    std::vector<int32_t> win(3 * (size_t)cap), flags(cap), cseg(cap);
+    std::vector<float> cseed(cap);
+    ffn_turn_request rq;
+    std::memset(&rq, 0, sizeof(rq));
+    for (int k = 0; k < 3; ++k) rq.min_boundary_dist[k] = a_.min_boundary_dist[k];
+    rq.do_init = 1;
+    rq.init_value = a_.init_value;
+    // `owed`: the last record's segment still awaits its commit / marker, which
+    // the next turn makes (rq holds them)
+    bool owed = false;
+    int rc = FFN_OK;
+    if (a_.resume) {
+      if (!sl_.in_segment) return FFN_ERR_STATE;
+      rc = segment(nullptr, &rq, &owed);
+    } else {
+      sl_.in_segment = false;
+    }
+    while (rc == FFN_OK) {
+      // (never before one attempt: every call makes progress)
+      const bool go_on = attempts_ == 0 || !budget_spent();
+      const int n = go_on ? window(win.data(), cap) : 0;
+      if (!owed && n == 0) {  // nothing to ask the device
+        if (!go_on) break;
+        if (idx_ >= a_.num_seeds) {
+          out_->exhausted = 1;
+          break;
+        }
+        ++out_->rejected_invalid;  // its FoV leaves the canvas (inference.py:329)
+        ++idx_;
+        continue;
+      }
+      rq.num_candidates = n;
+      ffn_turn_result tr;
+      const int64_t room = a_.max_overlaps - out_->num_overlaps;
+      rc = dev_.turn(rq, win.data(), &tr, (int32_t)std::min<int64_t>(room, INT32_MAX),
+                     a_.overlap_ids + out_->num_overlaps,
+                     a_.overlap_counts + out_->num_overlaps, flags.data(), cseed.data(),
+                     cseg.data());
+      if (rc) break;
+      ++out_->turns;
+      if (owed) settle(tr, &rq);
+      owed = false;
+      if (!go_on) break;
+      int chosen = -1;
+      for (int k = 0; k < n && chosen < 0; ++k) {
+        if (flags[k] == 3) break;  // after the chosen one: not looked at
+        ++idx_;
+        switch (flags[k]) {
+          case 0: chosen = k; break;
+          case 1: ++out_->rejected_invalid, ++out_->rejected_segmented; break;
+          case 2: ++out_->rejected_too_close; break;
+          default: ++out_->rejected_restricted; break;
+        }
+      }
+      if (chosen >= 0) rc = segment(&win[3 * (size_t)chosen], &rq, &owed);
+    }
+    out_->next_seed = idx_;
+    out_->in_segment = sl_.in_segment ? 1 : 0;
+    out_->restricted_skips = st_.skip_restricted;
+    st_.skip_restricted = 0;
+    out_->seconds = since(t0_);
+    return rc;
+  }
+
+ private:
+  typedef std::chrono::steady_clock Clock;
+  static double since(Clock::time_point t) {
+    return std::chrono::duration<double>(Clock::now() - t).count();
+  }
+
+  bool budget_spent() const {
+    const double s = since(t0_);
+    return (a_.max_segments > 0 && attempts_ >= a_.max_segments) ||
+           (a_.max_ms > 0 && s * 1e3 >= a_.max_ms) ||
+           (a_.has_deadline && s >= a_.deadline_s) ||
+           out_->num_records >= a_.max_records ||
+           // the commit that is owed and the one after it: up to max id pairs each
+           a_.max_overlaps - out_->num_overlaps < 2 * ((int64_t)max_id_ + 1);
+  }
+
+  bool in_bounds(const int32_t* p) const {
+    for (int k = 0; k < 3; ++k)
+      if (p[k] - a_.segment.margin_zyx[k] < 0 ||
+          p[k] + a_.segment.margin_zyx[k] >= a_.segment.shape_zyx[k])
+        return false;
+    return true;
+  }
+
+  // DeviceCanvas._upcoming_seeds: the next seeds of the list, up to the first whose
+  // FoV leaves the canvas or that the window already holds (the turn answers by
+  // coordinate)
+  int window(int32_t* win, int cap) {
+    listed_.clear();
+    int n = 0;
+    for (int64_t i = idx_; i < a_.num_seeds && n < cap; ++i, ++n) {
+      const int32_t* p = a_.seeds + 3 * i;
+      if (!in_bounds(p) || !listed_.insert(Coord{p[0], p[1], p[2]}).second) break;
+      std::memcpy(win + 3 * n, p, 12);
+    }
+    return n;
+  }
+
+  // One segment attempted at `start` (nullptr: the interrupted one, resumed); what
+  // the next turn has to do about it goes into *rq.
+  int segment(const int32_t* start, ffn_turn_request* rq, bool* owed) {
+    ffn_seed_record& rec = sl_.rec;
+    ffn_segment_params p = a_.segment;
+    p.max_steps = 0;
+    const int resume = start ? 0 : 1;
+    if (start) {
+      std::memset(&rec, 0, sizeof(rec));
+      for (int k = 0; k < 3; ++k)
+        rec.pos[k] = p.init_min_pos[k] = p.init_max_pos[k] = start[k];
+      p.initial_start_logit = a_.init_value;  // the turn has just written it
+    }
+    const Clock::time_point t = Clock::now();
+    ffn_segment_result res;
+    SegmentLoop<Dev> loop(dev_, st_, p);
+    const int rc = loop.run(rec.pos, resume, &res);
+    rec.seconds += since(t);
+    res.num_steps += rec.segment.num_steps;  // the legs before an error
+    res.skip_threshold += rec.segment.skip_threshold;
+    res.skip_invalid_pos += rec.segment.skip_invalid_pos;
+    res.gate_rejects += rec.segment.gate_rejects;
+    rec.segment = res;
+    sl_.in_segment = rc != FFN_OK;
+    if (rc) return rc;
+    ++attempts_;
+    *owed = true;
+    if (res.num_steps <= 0) {  // (inference.py:592-597)
+      rec.outcome = FFN_SEED_NO_STEPS;
+      *owed = false;
+    } else if (res.start_logit_known && res.start_logit < p.step.move_threshold) {
+      rec.outcome = FFN_SEED_WEAK;  // (inference.py:600-606)
+      rq->mark_mode = 1;
+    } else {  // the box the FFN changed (inference.py:608-612), counted and assigned
+      rec.outcome = FFN_SEED_TOO_SMALL;  // until the turn says otherwise
+      rq->do_commit = 1;
+      for (int k = 0; k < 3; ++k) {
+        rq->lo[k] = std::max(res.min_pos[k] - a_.half_pred[k], 0);
+        rq->hi[k] = std::min(res.max_pos[k] + a_.half_pred[k] + 1, p.shape_zyx[k]);
+      }
+      rq->segment_threshold = a_.segment_threshold;
+      rq->min_segment_size = a_.min_segment_size;
+      rq->segment_id = next_id_;
+      rq->max_existing_id = max_id_;
+      rq->mark_mode = 2;
+    }
+    for (int k = 0; k < 3; ++k) rq->mark_pos[k] = rec.pos[k];
+    a_.records[out_->num_records++] = rec;
+    return FFN_OK;
+  }
+
+  // the turn that was owed has been made: the last record's outcome
+  void settle(const ffn_turn_result& tr, ffn_turn_request* rq) {
+    ffn_seed_record& rec = a_.records[out_->num_records - 1];
+    if (rq->do_commit) {
+      rec.raw_segmented_voxels = tr.counts.raw_segmented_voxels;
+      rec.actual_segmented_voxels = tr.counts.actual_segmented_voxels;
+      rec.num_overlaps = tr.counts.num_overlapped_ids;
+      rec.first_overlap = out_->num_overlaps;
+      out_->num_overlaps += rec.num_overlaps;
+      if (tr.committed) {
+        rec.outcome = FFN_SEED_COMMITTED;
+        rec.segment_id = next_id_;
+        max_id_ = std::max(max_id_, next_id_);
+        ++next_id_;
+      }
+    }
+    rq->do_commit = 0;
+    rq->mark_mode = 0;
+  }
+
+  Dev& dev_;
+  SegmentState& st_;
+  SeedLoopState& sl_;
+  const ffn_seed_loop_args& a_;
+  ffn_seed_loop_result* out_;
+  Clock::time_point t0_;
+  int64_t idx_ = 0;
+  int32_t next_id_ = 0, max_id_ = 0, attempts_ = 0;
+  std::unordered_set<Coord, CoordHash> listed_;
+};
+
+// ffn_canvas_segment_all's argument checks, shared with the test shim.
+inline bool seed_loop_args_ok(const ffn_seed_loop_args& a) {
+  return a.num_seeds >= 0 && (a.seeds || a.num_seeds == 0) && a.first_seed >= 0 &&
+         a.first_seed <= a.num_seeds && a.turn_candidates >= 1 &&
+         a.turn_candidates <= 4096 && a.max_records >= 1 && a.records &&
+         a.overlap_ids && a.overlap_counts && a.max_existing_id >= 0 &&
+         a.next_segment_id > 0 &&
+         a.max_overlaps >= 2 * ((int64_t)a.max_existing_id + 1);
+}
 
 // The segment loops of n canvases advanced TOGETHER (ffn_canvas_segment_many;
 // config C3: the reference's client threads + batching server thread,

@@ -110,6 +110,50 @@ def segment_many_with_retry(once, n, sarr, parr, rarr, before, fallback):
   return rc, res, fin
 
 
+def seed_loop_with_retry(once, args, fallback):
+  """One `ffn_canvas_segment_all` call plus the handling of a voided step, shared
+  by DeviceCanvasHandle and the CPU shim of the tests.  once(args, result) -> rc
+  makes the call; fallback(rc) as in `segment_many_with_retry`.  The voided step
+  changed nothing and its segment stays resumable: the call is made again with
+  resume = 1 behind the records it has already written, with what is left of its
+  budget, and the result covers all legs (`args` is left as the caller set it)."""
+  total = _lib.SeedLoopResult()
+  saved = _lib.SeedLoopArgs.from_buffer_copy(args)
+  summed = ('rejected_invalid', 'rejected_segmented', 'rejected_restricted',
+            'rejected_too_close', 'restricted_skips', 'seconds', 'turns')
+  recs = ctypes.cast(args.records, ctypes.POINTER(_lib.SeedRecord))
+  try:
+    for attempt in range(MAX_VOID_REPEATS + 1):
+      res = _lib.SeedLoopResult()
+      rc = once(args, res)
+      n0, o0 = total.num_records, total.num_overlaps
+      for k in range(n0, n0 + res.num_records):
+        recs[k].first_overlap += o0
+        if recs[k].outcome == _lib.SEED_COMMITTED:
+          args.max_existing_id = max(args.max_existing_id, recs[k].segment_id)
+          args.next_segment_id = recs[k].segment_id + 1
+      for name in summed:
+        setattr(total, name, getattr(total, name) + getattr(res, name))
+      total.num_records = n0 + res.num_records
+      total.num_overlaps = o0 + res.num_overlaps
+      total.next_seed, total.exhausted = res.next_seed, res.exhausted
+      total.in_segment = res.in_segment
+      if rc not in _lib.ERR_VOIDED or attempt == MAX_VOID_REPEATS:
+        return rc, total
+      fallback(rc)
+      args.resume = 1
+      args.first_seed = res.next_seed
+      if saved.max_segments > 0:
+        args.max_segments = max(saved.max_segments - total.num_records, 1)
+      args.records = saved.records + total.num_records * ctypes.sizeof(_lib.SeedRecord)
+      args.max_records = saved.max_records - total.num_records
+      args.overlap_ids = saved.overlap_ids + 4 * total.num_overlaps
+      args.overlap_counts = saved.overlap_counts + 8 * total.num_overlaps
+      args.max_overlaps = saved.max_overlaps - total.num_overlaps
+  finally:
+    ctypes.pointer(args)[0] = saved
+
+
 class HipEngine:
   """One GPU + one stream + the conv-stack weights (include/ffn_hip.h)."""
 
@@ -521,6 +565,19 @@ class DeviceCanvasHandle:
     params.max_steps = budget
     for name in summed:
       setattr(res, name, getattr(res, name) + before[name])
+    check(rc)
+    return res
+
+  def segment_all(self, args: '_lib.SeedLoopArgs') -> '_lib.SeedLoopResult':
+    """ffn_canvas_segment_all: the seed loop of `Canvas.segment_all` inside the
+    library, from `args.first_seed` until the list or the call's budget ends;
+    the records of the segments attempted are in `args.records[:num_records]`.
+    A voided step (`HipEngine.voided`) is dealt with as in `segment_at` and the
+    call resumed: the result then covers all its legs, every step once."""
+    rc, res = seed_loop_with_retry(
+        lambda a, r: self._lib.ffn_canvas_segment_all(self._h, ctypes.byref(a),
+                                                      ctypes.byref(r)),
+        args, self.engine.voided)
     check(rc)
     return res
 

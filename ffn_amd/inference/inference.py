@@ -848,11 +848,7 @@ class DeviceCanvas(Canvas):
     device does not see -- no restrictor masks it has not been given, no timed
     checkpoint about to be taken, no probability map, the stock validity
     test."""
-    ok = self.__dict__.get('_turn_static')
-    if ok is None:
-      ok = (hasattr(self._handle, 'segment_turn') and
-            not self.keep_probability_maps and self._restrictor_ok())
-      self._turn_static = ok
+    ok = self._turn_possible()
     # A timed checkpoint is taken BETWEEN the loop's questions, and a turn moves
     # the canvas past them (the next seed initialised, too-close seeds marked).
     # So: no turn while a checkpoint is DUE -- the loop then asks its questions
@@ -860,7 +856,18 @@ class DeviceCanvas(Canvas):
     # and no checkpoint while a turn's answers are still being used up
     # (`_maybe_save_checkpoint` below: it waits for the next opportunity, where
     # this test keeps the turn from running).
-    return (ok and not self._checkpoint_due() and self.TURN_CANDIDATES > 0 and
+    return ok and not self._checkpoint_due() and self._turn_unhooked()
+
+  def _turn_possible(self) -> bool:
+    ok = self.__dict__.get('_turn_static')
+    if ok is None:
+      ok = (hasattr(self._handle, 'segment_turn') and
+            not self.keep_probability_maps and self._restrictor_ok())
+      self._turn_static = ok
+    return ok
+
+  def _turn_unhooked(self) -> bool:
+    return (self.TURN_CANDIDATES > 0 and
             getattr(self.is_valid_pos, '__func__', None)
             is DeviceCanvas.is_valid_pos)
 
@@ -1106,6 +1113,194 @@ class DeviceCanvas(Canvas):
             getattr(self.update_at, '__func__', None) is DeviceCanvas.update_at
             and getattr(self.is_valid_pos, '__func__', None)
             is DeviceCanvas.is_valid_pos)
+
+  # -- the whole seed loop inside the library ------------------------------------
+  #: class-wide switch (FFN_AMD_NATIVE_SEED_LOOP=0 in the environment turns it off)
+  NATIVE_SEED_LOOP = os.environ.get('FFN_AMD_NATIVE_SEED_LOOP', '1') != '0'
+  #: budget of one `ffn_canvas_segment_all` call: segments attempted, milliseconds.
+  #: Between two calls the interpreter logs, saves a due checkpoint and sees a
+  #: signal; a call costs one extra turn and its share of Python: from 16 / 125 ms
+  #: up to no budget at all the rate of a 250^3 pass (17 calls at the default)
+  #: does not depend on the value (profiles/native_seed_loop_ab.txt)
+  SEED_LOOP_SEGMENTS = int(os.environ.get('FFN_AMD_SEED_LOOP_SEGMENTS', '32'))
+  SEED_LOOP_MS = float(os.environ.get('FFN_AMD_SEED_LOOP_MS', '250'))
+
+  def _seed_loop_ok(self, policy) -> bool:
+    """True if `ffn_canvas_segment_all` may run this canvas' seed loop: the
+    library's segment loop and turn may run (`_native_loop_ok`, `_turn_ok`), the
+    policy hands out a list the stock way, nothing the loop calls between two
+    segments is hooked (subclass, instance or patched class), no history is
+    kept and the ids in `origins` are what `_max_id` says."""
+    cls = type(self)
+    if not (self.NATIVE_SEED_LOOP and hasattr(self._handle, 'segment_all') and
+            self.reset_seed_per_segment and not self._keep_history):
+      return False
+    for name, stock in _SEED_LOOP_STOCK.items():
+      if name in self.__dict__ or getattr(cls, name, None) is not stock:
+        return False
+    if type(policy).__next__ is not seed_lib.BaseSeedPolicy.__next__:
+      return False
+    if self.origins and max(self.origins) > self._max_id:
+      return False
+    # (a checkpoint that is due does not stand in the way, as it does for a single
+    # turn: it is saved between two calls, where the canvas is between two seeds)
+    return (self._native_loop_ok() and self._turn_possible() and
+            self._turn_unhooked())
+
+  def segment_all(self, seed_policy=seed_lib.PolicyPeaks,
+                  partial_segment_iters=0):
+    """Canvas.segment_all; the seed loop runs inside the library
+    (`ffn_canvas_segment_all`) when nothing needs the interpreter between two
+    segments (`_seed_loop_ok`), else in Python as before."""
+    if partial_segment_iters:
+      return super().segment_all(seed_policy, partial_segment_iters)
+    policy = seed_policy(self)
+    if not self._seed_loop_ok(policy):
+      return super().segment_all(lambda canvas: policy)
+    return self._segment_all_native(policy)
+
+  def _segment_all_native(self, policy):
+    self.seed_policy = policy
+    if self._seed_policy_state is not None:
+      policy.set_state(self._seed_policy_state)
+      self._seed_policy_state = None
+    c = self.counters
+    with timer_counter(c, 'segment_all'):
+      calls = c['seed-policy-calls']
+      c['seed-policy-time-ms']  # (the keys TimedIter makes)
+      if not policy.ensure_coords():
+        calls.Increment()
+      else:
+        args, recs = self._seed_loop_args(policy)
+        while True:
+          self._maybe_save_checkpoint(partial_segment_iters=0)
+          self._seed_loop_call_args(args, policy)
+          self._invalidate_cache()
+          res = self._call(self._handle.segment_all, args)
+          #: calls of the library's seed loop this canvas has made
+          self.seed_loop_calls = self.__dict__.get('seed_loop_calls', 0) + 1
+          self._seed_loop_apply(args, res, recs, policy)
+          if res.exhausted:
+            calls.Increment()  # the next() that found the list at its end
+            break
+    self.log_info('Segmentation done.')
+    self._deregister_client()
+
+  def _seed_loop_args(self, policy):
+    """The constant part of ffn_seed_loop_args and the arrays its records go to."""
+    args = _lib.SeedLoopArgs()
+    seeds = np.ascontiguousarray(policy.coords, dtype=np.int32).reshape(-1, 3)
+    args._seeds = seeds  # (kept alive with the struct)
+    args.seeds = seeds.ctypes.data
+    args.num_seeds = len(seeds)
+    ctypes.pointer(args.segment)[0] = self._segment_params()
+    args.segment.max_steps = 0
+    mbd = self.options.min_boundary_dist
+    args.min_boundary_dist[:] = [int(mbd.z), int(mbd.y), int(mbd.x)]
+    args.init_value = float(self.options.init_activation)
+    args.segment_threshold = float(self.options.segment_threshold)
+    args.half_pred[:] = [int(v) // 2 for v in self._pred_size]
+    args.min_segment_size = int(self.options.min_segment_size)
+    args.turn_candidates = self.TURN_CANDIDATES
+    args.max_segments = self.SEED_LOOP_SEGMENTS
+    args.max_ms = self.SEED_LOOP_MS
+    # a record per attempt, and room for the legs of a voided step
+    n = (self.SEED_LOOP_SEGMENTS if self.SEED_LOOP_SEGMENTS > 0 else 256) + 8
+    recs = (_lib.SeedRecord * n)()
+    args.records = ctypes.addressof(recs)
+    args.max_records = n
+    return args, recs
+
+  def _seed_loop_call_args(self, args, policy):
+    """What changes from call to call: where to start, the ids, the deadline and
+    overlap arrays for whatever `_max_id` a call can reach."""
+    args.first_seed = int(policy.idx)
+    args.resume = 0
+    args.next_segment_id = self._max_id + 1
+    args.max_existing_id = self._max_id
+    need = 4 * (self._max_id + args.max_records + 2)
+    if args.max_overlaps < need:
+      args._ids = np.zeros(2 * need, np.int32)
+      args._counts = np.zeros(2 * need, np.int64)
+      args.overlap_ids = args._ids.ctypes.data
+      args.overlap_counts = args._counts.ctypes.data
+      args.max_overlaps = 2 * need
+    timed = self.checkpoint_path is not None and self.checkpoint_interval_sec > 0
+    args.has_deadline = 1 if timed else 0
+    args.deadline_s = (self.checkpoint_last + self.checkpoint_interval_sec -
+                       time.time()) if timed else 0.0
+
+  def _seed_loop_apply(self, args, res, recs, policy):
+    """The bookkeeping of the Python loop (`_segment_all_gen`, `_native_postlude`)
+    for one call's records, in their order."""
+    c = self.counters
+    consumed = int(res.next_seed) - int(policy.idx)
+    policy.idx = int(res.next_seed)
+    if consumed:
+      c['seed-policy-calls'].IncrementBy(consumed)
+    if res.rejected_invalid:
+      c['skip_invalid_pos'].IncrementBy(int(res.rejected_invalid))
+      self.gate_rejects += int(res.rejected_segmented)
+    if res.restricted_skips:
+      c['skip_restriced_pos'].IncrementBy(int(res.restricted_skips))
+    self.turns += int(res.turns)
+    self._turn_armed = True
+    last = None
+    for k in range(res.num_records):
+      rec = recs[k]
+      seg = rec.segment
+      pos = (int(rec.pos[0]), int(rec.pos[1]), int(rec.pos[2]))
+      n = int(seg.num_steps)
+      ms = rec.seconds * MSEC_IN_SEC
+      self.log_info('Starting segmentation at %r (zyx)', pos)
+      c['segment_at-loop-calls'].Increment()
+      c['segment_at-loop-time-ms'].IncrementBy(ms)
+      if n:
+        c['update_at-calls'].IncrementBy(n)
+        c['inference-calls'].IncrementBy(n)
+        c['predict-calls'].IncrementBy(n)
+        c['movement_policy-calls'].IncrementBy(n)
+        c['update_at-time-ms'].IncrementBy(ms)
+        c['inference-time-ms'].IncrementBy(ms)
+      if seg.skip_threshold:
+        c['skip_threshold'].IncrementBy(int(seg.skip_threshold))
+      if seg.skip_invalid_pos:
+        c['skip_invalid_pos'].IncrementBy(int(seg.skip_invalid_pos))
+      if seg.seed_got_too_weak:
+        c['seed_got_too_weak'].Increment()
+      self.gate_rejects += int(seg.gate_rejects)
+      last = (pos, seg)
+      if rec.outcome == _lib.SEED_NO_STEPS:
+        c['invalid-other-time-ms'].IncrementBy(ms)
+        self.log_info('Failed: num iters was %d', n)
+      elif rec.outcome == _lib.SEED_WEAK:
+        self.log_info('Failed: weak seed')
+        c['invalid-weak-time-ms'].IncrementBy(ms)
+      elif rec.outcome == _lib.SEED_TOO_SMALL:
+        self.log_info('Failed: too small: %d', int(rec.actual_segmented_voxels))
+        c['invalid-small-time-ms'].IncrementBy(ms)
+      else:
+        sid = int(rec.segment_id)
+        actual = int(rec.actual_segmented_voxels)
+        self._max_id = sid
+        c['voxels-segmented'].IncrementBy(actual)
+        c['voxels-overlapping'].IncrementBy(
+            int(rec.raw_segmented_voxels) - actual)
+        self.log_info('Created supervoxel:%d  seed(zyx):%s  size:%d  iters:%d',
+                      sid, pos, actual, n)
+        o = int(rec.first_overlap)
+        self.overlaps[sid] = np.array([args._ids[o:o + rec.num_overlaps],
+                                       args._counts[o:o + rec.num_overlaps]])
+        self.origins[sid] = storage.OriginInfo(pos, n, rec.seconds)
+        c['valid-time-ms'].IncrementBy(ms)
+    if last is not None:  # the canvas as the last segment's postlude leaves it
+      pos, seg = last
+      self.reset_state(pos)
+      self._min_pos = np.array([int(v) for v in seg.min_pos])
+      self._max_pos = np.array([int(v) for v in seg.max_pos])
+      if seg.start_logit_known:
+        self._cached_start = (pos, float(seg.start_logit))
+      self.t_last_predict = time.time()
 
   def _segment_params(self):
     sp = self.__dict__.get('_seg_params')
@@ -1385,6 +1580,15 @@ class DeviceCanvas(Canvas):
     # a restored canvas may be inside a segment (partial_segment_iters): no turn
     # -- it would re-initialise the seed -- before that segment has ended
     self._turn_armed = False
+
+
+#: what the library's seed loop stands in for: a canvas on which any of these is
+#: not the stock function (a subclass, an instance hook, a patched class) keeps the
+#: Python seed loop, which calls them (`DeviceCanvas._seed_loop_ok`)
+_SEED_LOOP_STOCK = {
+    name: getattr(DeviceCanvas, name)
+    for name in ('_segment_at_native', '_segment_at_gen', '_segment_all_gen',
+                 '_commit', '_turn', 'init_seed', '_mark_excluded', '_too_close')}
 
 
 class NativeSegment:

@@ -47,17 +47,24 @@ class BaseSeedPolicy:
   def __iter__(self):
     return self
 
-  def __next__(self):
-    """Next seed as (z, y, x); seeds too close to the border are dropped early."""
+  def ensure_coords(self) -> bool:
+    """Makes the list on first use, seeds too close to the border dropped;
+    False: the policy has none."""
     if self.coords is None:
       self.init_coords()
       if self.coords is None:
-        raise StopIteration()
+        return False
       if self.coords.size:
         margin = np.array(self.canvas.margin)[np.newaxis, ...]
         self.coords = self.coords[np.all(
             (self.coords - margin >= 0) &
             (self.coords + margin < self.canvas.shape), axis=1), :]
+    return True
+
+  def __next__(self):
+    """Next seed as (z, y, x); seeds too close to the border are dropped early."""
+    if not self.ensure_coords():
+      raise StopIteration()
     while self.idx < self.coords.shape[0]:
       curr = self.coords[self.idx, :]
       self.idx += 1

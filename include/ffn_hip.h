@@ -339,6 +339,91 @@ int ffn_canvas_segment_turn(ffn_canvas* canvas, const ffn_turn_request* request,
                             int32_t* cand_flags, float* cand_seed,
                             int32_t* cand_seg);
 
+/* The SEED loop of Canvas.segment_all (inference.py:573-660) inside the library:
+ * turn, segment, turn, ... over a list of seeds, with no caller between two
+ * segments.  One turn tests the next `turn_candidates` seeds of the list (the
+ * window ends in front of a seed whose FoV leaves the canvas, or one it already
+ * holds) and initialises the first that passes; ffn_canvas_segment_at runs from
+ * it; the weak-seed test (start logit < step.move_threshold, inference.py:600)
+ * and the commit box (visited extents +- half_pred, clipped) follow; the NEXT
+ * turn commits or marks and tests the following seeds in the same device
+ * sequence.  Decisions, device calls and their order are those of
+ * DeviceCanvas._turn / _segment_at_native / _commit.
+ *
+ * A call ends when the list does, or at the first segment boundary at which
+ * max_segments attempts have been made, max_ms have passed or the deadline has
+ * (never before one attempt, so every call makes progress).  At every FFN_OK
+ * return the canvas is BETWEEN TWO SEEDS: the last attempted segment is
+ * committed or marked (the last turn of such a call has no candidates), no seed
+ * is initialised and none tested ahead -- seeds[0 .. next_seed) are dealt with,
+ * the others untouched.  On an error inside a segment (FFN_ERR_RANGE,
+ * FFN_ERR_FLOW: ffn_canvas_segment_at) the call returns it with the records
+ * made so far and in_segment = 1: deal with it and call again with resume = 1
+ * (first_seed = the next_seed returned); that segment's record then comes
+ * first and counts every step once. */
+#define FFN_SEED_NO_STEPS  0   /* the loop made no step ("num iters was 0")      */
+#define FFN_SEED_WEAK      1   /* start logit below move_threshold: marked -1    */
+#define FFN_SEED_TOO_SMALL 2   /* < min_segment_size voxels: marked -1           */
+#define FFN_SEED_COMMITTED 3   /* voxels assigned segment_id                     */
+
+typedef struct ffn_seed_record {   /* one segment ATTEMPTED                      */
+  int32_t pos[3];                  /* its seed                                   */
+  int32_t outcome;                 /* FFN_SEED_*                                 */
+  int32_t segment_id;              /* committed: its id, else 0                  */
+  int32_t num_overlaps;            /* (id, count) pairs of this record, at       */
+  int64_t first_overlap;           /*   overlap_ids / _counts[first_overlap ..)  */
+  int64_t raw_segmented_voxels;    /* ffn_commit_counts of its commit (0 when    */
+  int64_t actual_segmented_voxels; /*   none was tried)                          */
+  double  seconds;                 /* wall clock of the attempt, init to loop end */
+  ffn_segment_result segment;      /* the loop's tallies, over all its legs      */
+} ffn_seed_record;
+
+typedef struct ffn_seed_loop_args {
+  const int32_t* seeds;            /* [num_seeds][3] zyx, the policy's list      */
+  int64_t num_seeds;
+  int64_t first_seed;              /* index to start at                          */
+  ffn_segment_params segment;      /* max_steps = 0; init_* and initial_start_logit
+                                      are set per segment by the loop            */
+  int32_t min_boundary_dist[3];    /* the turn's constants (ffn_turn_request)    */
+  float   init_value;              /* init_activation                            */
+  float   segment_threshold;
+  int32_t half_pred[3];            /* pred_size // 2 (inference.py:608)          */
+  int64_t min_segment_size;
+  int32_t next_segment_id;         /* id of the next commit; then + 1            */
+  int32_t max_existing_id;         /* largest id in the canvas                   */
+  int32_t turn_candidates;         /* seeds tested per turn, >= 1                */
+  int32_t resume;                  /* 1: finish the segment an error interrupted */
+  int32_t max_segments;            /* budget of this call; <= 0: none            */
+  int32_t has_deadline;            /* deadline_s is set                          */
+  double  max_ms;                  /* <= 0: none                                 */
+  double  deadline_s;              /* seconds from the call's start              */
+  int32_t max_records;             /* capacity of records (>= 1)                 */
+  int32_t reserved;
+  ffn_seed_record* records;
+  int64_t max_overlaps;            /* capacity of the two arrays below, at least
+                                      max_existing_id + 1                        */
+  int32_t* overlap_ids;
+  int64_t* overlap_counts;
+} ffn_seed_loop_args;
+
+typedef struct ffn_seed_loop_result {
+  int64_t next_seed;               /* seeds[0 .. next_seed) are consumed         */
+  int64_t num_overlaps;            /* pairs written                              */
+  int64_t rejected_invalid;        /* seeds refused: FoV outside / segmented,    */
+  int64_t rejected_segmented;      /*   of them already segmented (gate rejects) */
+  int64_t rejected_restricted;     /*   vetoed by the restrictor,                */
+  int64_t rejected_too_close;      /*   within min_boundary_dist (marked -1)     */
+  int64_t restricted_skips;        /* ffn_canvas_take_restricted_skips, taken    */
+  double  seconds;                 /* wall clock of the call                     */
+  int32_t num_records;
+  int32_t turns;                   /* turns made                                 */
+  int32_t exhausted;               /* the list has ended                         */
+  int32_t in_segment;              /* an error left a segment to resume          */
+} ffn_seed_loop_result;
+
+int ffn_canvas_segment_all(ffn_canvas* canvas, const ffn_seed_loop_args* args,
+                           ffn_seed_loop_result* result);
+
 /* MovementRestrictor (movement.py:247-336) on the canvas.  Two bits per voxel p:
  *   pos_blocked(p)  = mask[p] != 0, or any non-zero voxel of shift_mask (the
  *                     REDUCED, thresholded mask, [Zs][Ys][Xs]) in the box
