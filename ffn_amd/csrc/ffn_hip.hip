@@ -1073,12 +1073,16 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
     int rc = set_lds_attr<false, false, false>(caps.lds_bytes);
     if (!rc) rc = set_lds_attr<true, true, false>(caps.lds_bytes);
     if (!rc) rc = set_lds_attr<false, false, true>(caps.lds_bytes);
-    if (!rc) rc = set_lds_attr_c<false, false, false>(caps.lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<true, true, false>(caps.lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true>(caps.lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 8>(caps.lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 16>(caps.lds_bytes_c);
-    if (!rc) rc = set_lds_attr_c<false, false, true, 24>(caps.lds_bytes_c);
+    // conv32c only where it takes the FoV (set_conv_variant refuses 2 elsewhere): rows past
+    // 119 voxels put lds_bytes_c beyond what a workgroup may ask for, and asking failed
+    // the creation of an engine that conv32 and the split-product kernels can serve
+    const bool c_ok = caps.exact_variant == 2;
+    if (!rc && c_ok) rc = set_lds_attr_c<false, false, false>(caps.lds_bytes_c);
+    if (!rc && c_ok) rc = set_lds_attr_c<true, true, false>(caps.lds_bytes_c);
+    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true>(caps.lds_bytes_c);
+    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 8>(caps.lds_bytes_c);
+    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 16>(caps.lds_bytes_c);
+    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 24>(caps.lds_bytes_c);
     if (!rc && caps.d_ok) rc = set_lds_attr_d(caps.lds_bytes_d);
     if (!rc && caps.e_ok) rc = set_lds_attr_e(caps.lds_bytes_e);
     if (!rc && caps.m_ok) rc = set_lds_attr_m();

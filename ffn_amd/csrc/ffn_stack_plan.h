@@ -150,6 +150,9 @@ inline ConvCaps conv_caps(const Geom& g, int depth) {
   c.gp = g;
   if (!m_fits(g)) {
     // shortest axis last (= the row direction), the other two in their order
+    // (tools/fov_edges.py, every odd FoV up to 131 per axis with V <= 70,000: (2,0,1) and
+    // (2,1,0) are chosen by none of them -- an earlier row has rows as short and fits
+    // wherever they do; (1,0,2) only by the columns 73 x 3 x 3 ... 131 x 3 x 3)
     static const int kPerms[5][3] = {{0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
     int best = -1;
     for (int k = 0; k < 5; ++k) {

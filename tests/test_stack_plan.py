@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import fov_edges
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 CAPS_FIELDS = ['fz', 'fy', 'fx', 'XS', 'oa0', 'oa1', 'oa2', 'permuted', 'nchunks_c',
@@ -33,6 +35,10 @@ SCHED = [[0, 1, 8, 9, 16, 18, 19], [2, 3, 10, 11, 17, 20, 21],
 FOV33 = ((33, 33, 33), (8, 8, 8), 12)
 FOV_C5 = ((21, 41, 41), (5, 10, 10), 3)
 FOV17 = ((17, 17, 17), (4, 4, 4), 12)
+# the geometries at the limits of the rules (tests/fov_edges.py), at the depth the GPU
+# tests run them with
+EDGE_CASES = [pytest.param(fov, deltas, 2, id=name) for name, fov, deltas, _ in fov_edges.EDGES]
+GEOMETRIES = [FOV33, FOV_C5, FOV17] + EDGE_CASES
 
 
 @pytest.fixture(scope='module')
@@ -149,7 +155,7 @@ def _expected(fov, depth):
   return e
 
 
-@pytest.mark.parametrize('fov,deltas,depth', [FOV33, FOV_C5, FOV17])
+@pytest.mark.parametrize('fov,deltas,depth', GEOMETRIES)
 def test_spans_flags_and_layout(shim, fov, deltas, depth):
   c = Caps(shim, fov, deltas, depth)
   want = _expected(fov, depth)
@@ -160,13 +166,21 @@ def test_spans_flags_and_layout(shim, fov, deltas, depth):
     assert getattr(c, name) == want[name], (name, getattr(c, name), want[name])
   assert c.lds_bytes_c == 2 * c.Rc * 40 * 4
   assert c.lds_bytes_d == max(3 * 128 * c.Rc_k, 4 * D_CHUNK * 144 + 64)
+  facts = _edge_facts(fov, depth)
+  assert (c.nchunks_m, c.nchunks_k, c.lds_bytes) == (
+      facts['nchunks_m'], facts['nchunks_k'], facts['lds_bytes'])
+  if c.m_ok and c.nchunks_m > 256:  # (the tail counts exist with a tail, taken or not)
+    assert (c.n_main, c.n_tail, c.n_tail3) == (256, facts['n_tail'], facts['n_tail3'])
+  else:
+    assert (c.n_main, c.n_tail, c.n_tail3) == (0, 0, 0)
+  assert c.n_half == facts['n_half']
   if fov == FOV_C5[0]:
     assert c.permuted and c.fx == 21  # rows of 21
   if fov == FOV17[0]:
     assert c.nchunks_m <= 256 and not c.t_ok and c.n_main == 0 and not c.h_geom_ok
 
 
-@pytest.mark.parametrize('fov,deltas,depth', [FOV33, FOV_C5, FOV17])
+@pytest.mark.parametrize('fov,deltas,depth', GEOMETRIES)
 def test_tap_schedules(shim, fov, deltas, depth):
   """Entry [w * 8 + j] of a schedule is kz 128 rows + ((ky - 1) XS + (kx - 1)) 16 for
   the tap kSched[w][j]; wave 3's dummy seventh tap repeats the sixth, and only
@@ -215,6 +229,74 @@ def _plan_rules(c, variant, flow, flow_skip, tail_batched, batch_chunks, n):
     family, chunks = 'D160', c.nchunks_k
   resident = family in ('MT', 'H') and n == 1 and flow == 2 and flow_skip == 0
   return family, resident, tail_tiles, chunks
+
+
+def _edge_facts(fov, depth=2):
+  """What tests/fov_edges.py states about a geometry, from _span, _expected and the
+  constants at the top of this file alone (nothing from the shim).  A slack is the row
+  budget minus span + halo in the layout the rules choose."""
+  e = _expected(fov, depth)
+  q = tuple(fov[a] for a in e['oa'])
+  v, halo = fov[0] * fov[1] * fov[2], 2 * (q[2] + 2)
+  nm = -(-v // M_CHUNK)
+  rest = v - 256 * M_CHUNK
+  n_tail = -(-rest // 32) if nm > 256 else 0
+  return dict(
+      default=e['default_variant'], exact=e['exact_variant'], oa=e['oa'], Rc=e['Rc'],
+      Rc_k=e['Rc_k'], rck_raw=_span(q, D_CHUNK) + halo,
+      m_slack=M_ROWS - (_span(q, M_CHUNK) + halo),
+      e_slack=E_ROWS - (_span(q, E_CHUNK) + halo),
+      nchunks_m=nm, nchunks_k=-(-v // D_CHUNK), last_m=v - (nm - 1) * M_CHUNK,
+      n_tail=n_tail, n_tail3=-(-rest // 96) if nm > 256 else 0,
+      tail_voxels=rest - (n_tail - 1) * 32 if nm > 256 else 0,
+      n_half=-(-v // H_CHUNK) if e['t_ok'] else 0,
+      lds_bytes=3 * (160 + 2 * (fov[2] + 2)) * 32 * 4)
+
+
+@pytest.mark.parametrize('name', sorted(fov_edges.FACTS))
+def test_edge_geometries_are_still_edges(name):
+  """Each geometry of tests/fov_edges.py still has the property it is in the list for,
+  by brute force over its chunks and the constants above: a changed row budget or chunk
+  size must not turn an edge test into a mid-range one without anyone noticing."""
+  _, fov, _, what = fov_edges.BY_NAME[name]
+  got = _edge_facts(fov)
+  for key, want in fov_edges.FACTS[name].items():
+    assert got[key] == want, (
+        '%s %s (%s): %s is %s, stated %s -- the rules or their constants changed: re-run '
+        'tools/fov_edges.py and pick the geometry that has this property now' %
+        (name, fov, what, key, got[key], want))
+
+
+def test_edge_list_covers_what_the_six_hand_picked_fovs_do_not():
+  """The classes the list exists for, each met by at least one entry."""
+  facts = {name: _edge_facts(fov) for name, fov, _, _ in fov_edges.EDGES}
+  defaults = {f['default'] for f in facts.values()}
+  assert defaults == {0, 2, 6, 8, 9}
+  # (no geometry tools/fov_edges.py swept chooses (2,0,1) or (2,1,0))
+  assert {f['oa'] for f in facts.values()} == {(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0)}
+  assert {f['Rc_k'] for f in facts.values() if f['default'] >= 6} == {256, 288, 320}
+  assert {1, 256} <= {f['n_tail'] for f in facts.values() if f['default'] == 9}
+  assert any(f['m_slack'] == 0 for f in facts.values())
+  assert any(f['default'] == 9 and f['exact'] == 0 for f in facts.values())
+  assert 160 * 1024 - 3 * 2 * 128 < facts['widest']['lds_bytes'] <= 160 * 1024
+  assert _edge_facts(fov_edges.TOO_WIDE[1])['lds_bytes'] > 160 * 1024
+  for name, fov, deltas, _ in fov_edges.EDGES + [fov_edges.TOO_WIDE]:
+    assert all(f % 2 == 1 and f >= 3 and 2 * d + 1 <= f for f, d in zip(fov, deltas)), name
+
+
+@pytest.mark.parametrize('fov,deltas', [FOV33[:2], ((5, 5, 5), (1, 1, 1))])
+def test_depth_one_has_no_split_product_family(shim, fov, deltas):
+  """Depth 1 is conv0_a, conv0_b and the head: d_ok is false, so is everything built on
+  it, and the default is the exact-f32 kernel."""
+  c = Caps(shim, fov, deltas, 1)
+  want = _expected(fov, 1)
+  assert not (c.d_ok or c.e_ok or c.m_ok or c.t_ok or c.h_geom_ok)
+  assert not (want['d_ok'] or want['m_ok'] or want['t_ok'])
+  assert c.exact_variant == want['exact_variant'] == 2
+  assert c.default_variant == want['default_variant'] == c.exact_variant
+  assert c.k_ok == want['k_ok']  # (the geometry alone: 33^3 fits conv32d's slots)
+  two = Caps(shim, fov, deltas, 2)
+  assert two.default_variant == (9 if fov == FOV33[0] else 2)
 
 
 @pytest.mark.parametrize('clear_e_ok,clear_m_ok', [(False, False), (True, False),
