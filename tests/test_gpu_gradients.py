@@ -12,6 +12,13 @@ check the masks separately (pre-activations within 1e-4 of the f64 run's, sign
 flips only where |pre_f64| is below the measured distance and on at most
 0.01 % of the inputs): a comparison of two independent forward passes would
 trip over the ReLU kink.
+
+Exact cases.  The per-conv ops are plain f32, so on integer operands (x, dy, skip
+in [-3, 3], w, b in [-2, 2]) every partial sum in any order is an integer far
+below 2^24 -- y and dx sum 864 terms of at most 6 (+ bias and skip), dW at most
+2 * 9 * 11 * 13 = 2574 positions of at most 9, below 2^15 -- and the result must
+be the f64 oracle's bit for bit: no yardstick, np.array_equal.  The loss and the
+whole stack stay on the yardstick (sigmoid and log are not exact).
 """
 import ctypes
 
@@ -82,6 +89,28 @@ def conv_inputs(shape, cin, seed):
   return x, w, b, dy, skip
 
 
+def exact_conv_inputs(shape, cin, seed):
+  """conv_inputs with integers: x, dy, skip in [-3, 3], w, b in [-2, 2]"""
+  rng = np.random.RandomState(seed)
+  act = shape + (32,)
+  ints = lambda lo, hi, size: rng.randint(lo, hi + 1, size).astype(np.float32)
+  x = (ints(-3, 3, shape), ints(-3, 3, shape)) if cin == 2 else ints(-3, 3, act)
+  return (x, ints(-2, 2, (3, 3, 3, cin, 32)), ints(-2, 2, (32,)), ints(-3, 3, act),
+          ints(-3, 3, act))
+
+
+def exactly(label, got, want64):
+  """got (f32, from the GPU) is the f64 oracle's value, which is an f32 value"""
+  want64 = np.asarray(want64, np.float64)
+  want = want64.astype(np.float32)
+  assert np.array_equal(want.astype(np.float64), want64), label
+  assert np.abs(want64).max() > 0, label
+  differ = int((got != want).sum())
+  print('%-44s exact case: %d of %d differ from f64, max |value| %g' %
+        (label, differ, want.size, np.abs(want64).max()))
+  assert got.shape == want.shape and differ == 0, label
+
+
 def oracle_pair(*args, **kwargs):
   import torch
   return (ref.conv_case(*args, dtype=torch.float64, **kwargs),
@@ -97,17 +126,39 @@ def test_conv_forward(ops, dev, torch, shape, cin, relu_in, use_skip):
   x, w, b, dy, skip = conv_inputs(shape, cin, seed=1)
   r64, r32 = oracle_pair(x, w, b, dy, relu_in=relu_in,
                          skip=skip if use_skip else None)
-  xd = [dev(p) for p in x] if cin == 2 else [dev(x), None]
-  wd, bd, sd = dev(w), dev(b), dev(skip) if use_skip else None
-  runs = []
-  for _ in range(2):
-    y = torch.full(shape + (32,), np.nan, dtype=torch.float32, device='cuda:0')
-    torch.cuda.synchronize()
-    ops.conv_forward(shape[0], shape[1:], cin, xd[0], xd[1], relu_in, wd, bd,
-                     sd, y)
-    runs.append(host(y))
+  runs = [run_forward(ops, dev, torch, shape, cin, x, relu_in, w, b,
+                      skip if use_skip else None) for _ in range(2)]
   assert np.array_equal(runs[0], runs[1])
   yardstick('conv_forward %s cin %d' % (shape, cin), runs[0], r64[0], r32[0])
+  check_forward_exact(ops, dev, torch, shape, cin, relu_in, use_skip)
+
+
+def run_forward(ops, dev, torch, shape, cin, x, relu_in, w, b, skip):
+  xd = [dev(p) for p in x] if cin == 2 else [dev(x), None]
+  wd, bd, sd = dev(w), dev(b), None if skip is None else dev(skip)
+  y = torch.full(shape + (32,), np.nan, dtype=torch.float32, device='cuda:0')
+  torch.cuda.synchronize()
+  ops.conv_forward(shape[0], shape[1:], cin, xd[0], xd[1], relu_in, wd, bd, sd,
+                   y)
+  return host(y)
+
+
+def check_forward_exact(ops, dev, torch, shape, cin, relu_in, use_skip):
+  x, w, b, dy, skip = exact_conv_inputs(shape, cin, seed=11)
+  skip = skip if use_skip else None
+  r64 = ref.conv_case(x, w, b, dy, relu_in=relu_in, skip=skip,
+                      dtype=torch.float64)
+  got = run_forward(ops, dev, torch, shape, cin, x, relu_in, w, b, skip)
+  exactly('conv_forward %s cin %d' % (shape, cin), got, r64[0])
+
+
+# (1, 2, 3, 4): fewer positions than one tile of any of the three ops
+@pytest.mark.parametrize('use_skip', [False, True])
+@pytest.mark.parametrize('relu_in', [False, True])
+@pytest.mark.parametrize('cin', [2, 32])
+def test_conv_forward_exact_single_slice(ops, dev, torch, cin, relu_in,
+                                         use_skip):
+  check_forward_exact(ops, dev, torch, (1, 2, 3, 4), cin, relu_in, use_skip)
 
 
 # -- 2. conv backward to the input -------------------------------------------
@@ -126,13 +177,41 @@ def test_conv_backward_input(ops, dev, torch, shape, use_mask, accumulate):
       dx = dx + old.astype(dx.dtype)
     return dx
 
+  got = run_backward_input(ops, dev, torch, shape, dy, w, pre, old, use_mask,
+                           accumulate)
+  yardstick('conv_backward_input %s' % (shape,), got, finish(r64[1]),
+            finish(r32[1]))
+  check_backward_input_exact(ops, dev, torch, shape, use_mask, accumulate)
+
+
+def run_backward_input(ops, dev, torch, shape, dy, w, pre, old, use_mask,
+                       accumulate):
   dxd = dev(old) if accumulate else torch.full(
       shape + (32,), np.nan, dtype=torch.float32, device='cuda:0')
   torch.cuda.synchronize()
   ops.conv_backward_input(shape[0], shape[1:], dev(dy), dev(w),
                           dev(pre) if use_mask else None, accumulate, dxd)
-  yardstick('conv_backward_input %s' % (shape,), host(dxd), finish(r64[1]),
-            finish(r32[1]))
+  return host(dxd)
+
+
+def check_backward_input_exact(ops, dev, torch, shape, use_mask, accumulate):
+  x, w, b, dy, old = exact_conv_inputs(shape, 32, seed=12)
+  dx = ref.conv_case(x, w, b, dy, dtype=torch.float64)[1]
+  if use_mask:
+    dx = dx * (x > 0).astype(dx.dtype)
+  if accumulate:
+    dx = dx + old.astype(dx.dtype)
+  got = run_backward_input(ops, dev, torch, shape, dy, w, x, old, use_mask,
+                           accumulate)
+  exactly('conv_backward_input %s' % (shape,), got, dx)
+
+
+@pytest.mark.parametrize('accumulate', [False, True])
+@pytest.mark.parametrize('use_mask', [False, True])
+def test_conv_backward_input_exact_single_slice(ops, dev, torch, use_mask,
+                                                accumulate):
+  check_backward_input_exact(ops, dev, torch, (1, 2, 3, 4), use_mask,
+                             accumulate)
 
 
 # -- 3. conv backward to the weights -----------------------------------------
@@ -162,6 +241,12 @@ def test_conv_backward_weights(ops, dev, torch, shape, cin, relu_in):
   assert np.array_equal(first[1], again[1])
   yardstick('dW %s cin %d' % (shape, cin), first[0], r64[2], r32[2])
   yardstick('db %s cin %d' % (shape, cin), first[1], r64[3], r32[3])
+  x, w, b, dy, _ = exact_conv_inputs(shape, cin, seed=13)
+  r64 = ref.conv_case(x, w, b, dy, relu_in=relu_in, dtype=torch.float64)
+  dw, db = run_backward_weights(ops, dev, torch, shape, cin, x, relu_in, dy)
+  assert np.abs(r64[2]).max() < 2 ** 15
+  exactly('dW %s cin %d' % (shape, cin), dw, r64[2])
+  exactly('db %s cin %d' % (shape, cin), db, r64[3])
 
 
 @pytest.mark.parametrize('corner', ['first', 'last'])
