@@ -28,11 +28,13 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_coordinates.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_evaluation.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h'),
-           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_optimizer.h')]
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_optimizer.h'),
+           os.path.join(os.path.dirname(_HERE), 'include', 'ffn_metrics.h')]
 SOURCES = ['ffn_hip.hip', 'ffn_canvas.hip', 'ffn_options.hip', 'ffn_labels.hip',
            'ffn_seeds.hip', 'ffn_decision.hip', 'ffn_analysis.hip',
            'ffn_partitions.hip', 'ffn_coordinates.hip',
-           'ffn_evaluation.hip', 'ffn_gradients.hip', 'ffn_optimizer.hip']
+           'ffn_evaluation.hip', 'ffn_gradients.hip', 'ffn_optimizer.hip',
+           'ffn_metrics.hip']
 
 MAX_CANDIDATES = 16
 
@@ -496,6 +498,22 @@ SIGNATURES = {
     'ffn_optimizer_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double)]),
     'ffn_optimizer_last_timing_aggregate': (
         _I, [_P, ctypes.POINTER(ctypes.c_double)]),
+    # include/ffn_metrics.h
+    'ffn_metrics_create': (_I, [_I, ctypes.POINTER(_P)]),
+    'ffn_metrics_destroy': (None, [_P]),
+    'ffn_metrics_contingency': (
+        _I, [_P, _P, _I, _I, _P, _I, _I, ctypes.POINTER(ctypes.c_int64),
+             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _I,
+             ctypes.c_size_t, _P, _P, _P, ctypes.POINTER(ctypes.c_size_t)]),
+    'ffn_metrics_skeleton': (
+        _I, [_P, _P, _I, _I, ctypes.POINTER(ctypes.c_int64),
+             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+             ctypes.c_size_t, _P, _P, ctypes.c_size_t, _P, _P, ctypes.c_uint64,
+             _P, _P, ctypes.c_size_t, _P, _P, _P,
+             ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t, _P,
+             ctypes.POINTER(ctypes.c_size_t), _P, _P]),
+    'ffn_metrics_last_timing': (_I, [_P, ctypes.POINTER(ctypes.c_double),
+                                     ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 """What the Python handles over the side units of libffn_hip.so share
 (labels.LabelOps, seeding.Seeder, decision.DecisionOps, analysis.Analyzer,
-partitions.PartitionOps, coordinates.CoordinateOps,
+partitions.PartitionOps, coordinates.CoordinateOps, metrics.MetricOps,
 training.evaluation.EvaluationOps, training.gradients.GradientOps,
 training.optimizer.OptimizerOps): the handle lifecycle, the per-device default instances, and the retry of a call
 whose output arrays were too small.

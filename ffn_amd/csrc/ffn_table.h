@@ -1,7 +1,7 @@
 // Open-addressing hash table over u64 keys, shared by ffn_labels.hip (joint-id
 // histograms, relabelling), ffn_partitions.hip (label sizes), ffn_decision.hip
-// (per-pair minimum) and ffn_analysis.hip (per-point id counts).  Not part of
-// the C-ABI.
+// (per-pair minimum), ffn_analysis.hip (per-point id counts) and
+// ffn_metrics.hip (contingency and skeleton tables).  Not part of the C-ABI.
 //
 // A table is `mask + 1` (a power of two) u64 key slots, all kEmptyKey when
 // empty; the payload arrays are the caller's, indexed by the slot returned.

@@ -1,6 +1,6 @@
 // Host scaffold shared by the side units of libffn_hip.so (ffn_labels,
 // ffn_seeds, ffn_decision, ffn_analysis, ffn_partitions, ffn_coordinates,
-// ffn_evaluation, ffn_gradients, ffn_optimizer; not part of the C-ABI): the
+// ffn_evaluation, ffn_gradients, ffn_optimizer, ffn_metrics; not part of the C-ABI): the
 // error macros, grow-only buffers that free themselves, and the handle base with its create / destroy path
 // and event-pair timer.  Host code only.
 #ifndef FFN_UNIT_H_
