@@ -11,6 +11,7 @@ import ctypes
 import os
 import subprocess
 import threading
+import time
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
@@ -30,7 +31,10 @@ HEADERS = [HEADER,
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_gradients.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_optimizer.h'),
            os.path.join(os.path.dirname(_HERE), 'include', 'ffn_metrics.h')]
-SOURCES = ['ffn_hip.hip', 'ffn_canvas.hip', 'ffn_options.hip', 'ffn_labels.hip',
+# (the conv kernel families first: build() starts the units in this order, the longest
+# compiles in front -- profiles/stack_units_build.txt)
+SOURCES = ['ffn_stack_resident.hip', 'ffn_stack_m.hip', 'ffn_stack.hip', 'ffn_stack_d.hip',
+           'ffn_hip.hip', 'ffn_canvas.hip', 'ffn_options.hip', 'ffn_labels.hip',
            'ffn_seeds.hip', 'ffn_decision.hip', 'ffn_analysis.hip',
            'ffn_partitions.hip', 'ffn_coordinates.hip',
            'ffn_evaluation.hip', 'ffn_gradients.hip', 'ffn_optimizer.hip',
@@ -522,8 +526,8 @@ _lock = threading.Lock()
 
 def build(force: bool = False) -> str:
   """Compiles csrc/*.hip for gfx950 into csrc/libffn_hip.so (in-tree): one
-  object per source under csrc/build/ (stale ones only, in parallel), then the
-  link."""
+  object per source under csrc/build/ (stale ones only, at most MAX_JOBS -- 16 -- at a
+  time, in the order of SOURCES), then the link."""
   headers = HEADERS + [os.path.join(CSRC, name) for name in sorted(os.listdir(CSRC))
                        if name.endswith('.h')]
   hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
@@ -531,6 +535,7 @@ def build(force: bool = False) -> str:
     hipcc = 'hipcc'
   objdir = os.path.join(CSRC, 'build')
   os.makedirs(objdir, exist_ok=True)
+  max_jobs = max(1, int(os.environ.get('MAX_JOBS', 16)))
   jobs, objs = [], []
   for name in SOURCES:
     src = os.path.join(CSRC, name)
@@ -538,6 +543,8 @@ def build(force: bool = False) -> str:
     objs.append(obj)
     if (force or not os.path.exists(obj) or
         any(os.path.getmtime(obj) < os.path.getmtime(d) for d in [src] + headers)):
+      while sum(p.poll() is None for _, p in jobs) >= max_jobs:
+        time.sleep(0.05)
       jobs.append((name, subprocess.Popen(
           [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-c',
            src, '-o', obj], cwd=CSRC)))

@@ -1,5 +1,6 @@
 // The exact-f32 3x3x3 32->32 convs (conv_variant 0 and 2): v_mfma_f32_16x16x4_f32, bitwise the oracle's fmaf chain.
-// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
+// And the head where no conv takes it along (head_kernel: no template, so this header is
+// included by ffn_stack.hip alone, behind ffn_kernels.h, inside no namespace)
 #pragma once
 
 namespace ffn {
@@ -545,10 +546,62 @@ __global__ __launch_bounds__(kConvThreads, 2) void conv32c_kernel(ConvCArgs a) {
   }
 }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+// ---------------------------------------------------------------------------
+// head: ReLU -> 1x1x1 conv 32->1 + bias; logits = seed + update
+// (reference convstack_3d.py:51-54,91-94; model.py:168-183) and the count of
+// logits >= move_threshold that the disco test needs (inference.py:428-431).
+// 8 lanes per voxel: one coalesced 128-B line per voxel, xor-shuffle reduce.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void head_kernel(
+    const float* __restrict__ X, const float* __restrict__ in_seed,
+    float pad_value, const float* __restrict__ wl /*[32] + bias*/,
+    float move_thr, float* __restrict__ logits,
+    unsigned* __restrict__ block_count /*[n][gridDim.x]*/, Geom g) {
+  __shared__ unsigned wave_cnt[4];
+  const int item = blockIdx.y;
+  const int sub = threadIdx.x & 7;
+  const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + sub * 4);
+  const float bias = wl[kFeatures];
+  unsigned mine = 0;
+  for (int v0 = blockIdx.x * 32; v0 < g.V; v0 += gridDim.x * 32) {
+    const int v = v0 + (threadIdx.x >> 3);
+    float partial = 0.0f;
+    const bool live = v < g.V;
+    if (live) {
+      const int x = v % g.fx;
+      const int t = v / g.fx;
+      const int y = t % g.fy;
+      const int z = t / g.fy;
+      const size_t p = (size_t)z * g.plane + y * g.XS + x;
+      const f32x4 a = *reinterpret_cast<const f32x4*>(
+          X + (size_t)item * g.act_stride + p * kFeatures + sub * 4);
+      // max(0, .) is idempotent: correct for raw and pre-activated X
+      partial = fmaxf(a[0], 0.f) * w4[0];
+      partial = __builtin_fmaf(fmaxf(a[1], 0.f), w4[1], partial);
+      partial = __builtin_fmaf(fmaxf(a[2], 0.f), w4[2], partial);
+      partial = __builtin_fmaf(fmaxf(a[3], 0.f), w4[3], partial);
+    }
+    partial += __shfl_xor(partial, 1);
+    partial += __shfl_xor(partial, 2);
+    partial += __shfl_xor(partial, 4);
+    bool above = false;
+    if (live && sub == 0) {
+      float s = in_seed[(size_t)item * g.V + v];
+      if (s != s) s = pad_value;
+      const float lg = s + (partial + bias);
+      logits[(size_t)item * g.V + v] = lg;
+      above = lg >= move_thr;
+    }
+    mine += (unsigned)__popcll(__ballot(above));  // wave-uniform
+  }
+  // per-block partial count; the paste kernel sums them (no atomics on one hot
+  // address: those serialise at ~12 ns each, and no counter to zero per step)
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    block_count[item * gridDim.x + blockIdx.x] =
+        wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
 
 }  // namespace ffn

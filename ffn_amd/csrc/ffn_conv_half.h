@@ -1,6 +1,7 @@
 // conv32h / conv32hs: the split-product conv on 16-position tiles, 80-voxel workgroups -- two
 // independent hand-off chains per SIMD inside ONE FoV (conv_variant 10; measured, not the default).
-// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
+// (conv32hs_kernel is no template: included by ffn_stack_resident.hip alone, behind ffn_stack_units.h,
+// inside no namespace)
 #pragma once
 
 namespace ffn {

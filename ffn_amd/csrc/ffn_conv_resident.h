@@ -1,5 +1,6 @@
 // conv32ps: the conv stack of a single-FoV step as ONE resident launch (engine option flow = 2).
-// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
+// (templates only: ffn_stack_units.h includes it behind ffn_conv_split.h, inside no namespace;
+// ffn_stack_resident.hip alone instantiates the kernel)
 #pragma once
 
 namespace ffn {

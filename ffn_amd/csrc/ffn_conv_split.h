@@ -1,5 +1,6 @@
 // The split-product 3x3x3 32->32 convs (conv_variant 6 .. 9: conv32d, conv32m, conv32mt), their FLOW hand-off and the helpers they share.
-// (included by ffn_hip.hip alone, behind ffn_kernels.h, inside no namespace)
+// (templates only: included by every unit of the conv launch layer, ffn_stack_units.h, behind
+// ffn_kernels.h, inside no namespace; ffn_stack_d.hip and ffn_stack_m.hip instantiate its kernels)
 #pragma once
 
 namespace ffn {
@@ -59,9 +60,8 @@ namespace ffn {
 // (No memory operation of the compiler's precedes a DMA it must not wait for:
 // its own vmcnt for such a load would count none of them and drain the queue.)
 // ---------------------------------------------------------------------------
-// (kDChunk = 160, kDThreads = 256, kDRowB = 144: ffn_types.h)
+// (kDChunk = 160, kDThreads = 256, kDRowB = 144, kDTaps = 28: ffn_types.h)
 constexpr int kDTiles = 5;
-constexpr int kDTaps = 28;    // 27 + the all-zero tap
 constexpr int kDTapBytes = 2 * 2 * 1024;  // weight fragments of one tap (hi, res)
 
 // what changes from one conv of the stack to the next (a launch's own in
@@ -268,8 +268,7 @@ constexpr bool kPollMerged = FFN_POLL_MERGED != 0;
 // 32), 256 bytes apart -- polled words that share a line, or a memory channel,
 // with the words other workgroups publish slow both sides down (measured: four
 // flag stores per workgroup instead of one, or two polls in flight instead of
-// one, cost 10 - 25 % of the step).
-constexpr int kFlowStride = 64;  // words between two producers' words
+// one, cost 10 - 25 % of the step).  (kFlowStride = 64 words: ffn_types.h)
 
 // The lab's run-time plumbing (clock stamps, flow traces, the flow_debug bits) as the FLOW
 // bodies read it.  LAB = false is the production form of the resident stack
@@ -1489,28 +1488,16 @@ __device__ __forceinline__ void conv32m_body(const A& a, const LT& L,
   }
 }
 
-template <int KIND, bool ADD_SKIP, bool HEAD>
+// PRODUCTS (engine option mfma_products) = 1: the same launch with the one-product body
+template <int KIND, bool ADD_SKIP, bool HEAD, int PRODUCTS = 3>
 __global__ __launch_bounds__(kDThreads, 2) void conv32m_kernel(ConvDArgs a) {
   const int gc = (blockIdx.x & 7) * a.slots_per_xcd + (blockIdx.x >> 3);
   if (gc >= a.total_slots) return;
   const long long t0 = a.dbg_wgs ? wall_clock64() : 0;
   const int item = (int)__umulhi((unsigned)gc, a.magic_nchunks);
   const int chunk = gc - item * a.nchunks;
-  conv32m_body<KIND, ADD_SKIP, HEAD>(a, a.L, item, chunk * kMChunk, gc, gc == 0);
-  stamp_workgroup(a, a.L, t0);
-}
-
-// mfma_products = 1: the same launch with the one-product body (a kernel of its own
-// name, so that the three-product symbols and their code stay exactly as they are)
-template <int KIND, bool ADD_SKIP, bool HEAD>
-__global__ __launch_bounds__(kDThreads, 2) void conv32m1_kernel(ConvDArgs a) {
-  const int gc = (blockIdx.x & 7) * a.slots_per_xcd + (blockIdx.x >> 3);
-  if (gc >= a.total_slots) return;
-  const long long t0 = a.dbg_wgs ? wall_clock64() : 0;
-  const int item = (int)__umulhi((unsigned)gc, a.magic_nchunks);
-  const int chunk = gc - item * a.nchunks;
-  conv32m_body<KIND, ADD_SKIP, HEAD, false, false, 1>(a, a.L, item, chunk * kMChunk, gc,
-                                                      gc == 0);
+  conv32m_body<KIND, ADD_SKIP, HEAD, false, false, PRODUCTS>(a, a.L, item, chunk * kMChunk, gc,
+                                                             gc == 0);
   stamp_workgroup(a, a.L, t0);
 }
 
@@ -1546,7 +1533,8 @@ struct ConvTailMap {
   int taoff[4 * 8];           // the tail's aoff table (its rows per segment)
 };
 
-template <int KIND, bool ADD_SKIP, bool HEAD, int TNT, bool FLOW = false>
+// PRODUCTS = 1: main and tail bodies with the one product
+template <int KIND, bool ADD_SKIP, bool HEAD, int TNT, bool FLOW = false, int PRODUCTS = 3>
 __global__ __launch_bounds__(kDThreads, 2) void conv32mt_kernel(ConvDArgs a,
                                                                 ConvTailMap mp) {
   static_assert(!FLOW || TNT == 1, "FLOW: the single-FoV form");
@@ -1578,8 +1566,8 @@ __global__ __launch_bounds__(kDThreads, 2) void conv32mt_kernel(ConvDArgs a,
   if (main_wg) {
     const int c = xcd * mp.mains_per_xcd + r;
     if (c >= mp.n_main) return;
-    conv32m_body<KIND, ADD_SKIP, HEAD, FLOW>(a, a.L, item, c * kMChunk, item * slots + c,
-                                             blockIdx.x == 0 && a.dbg_wgs != 2);
+    conv32m_body<KIND, ADD_SKIP, HEAD, FLOW, false, PRODUCTS>(
+        a, a.L, item, c * kMChunk, item * slots + c, blockIdx.x == 0 && a.dbg_wgs != 2);
   } else {
     const int c = xcd * mp.tails_per_xcd + r;
     if (c >= mp.n_tail) return;
@@ -1589,50 +1577,7 @@ __global__ __launch_bounds__(kDThreads, 2) void conv32mt_kernel(ConvDArgs a,
     // W0, dz = -1, W1 in front of the first barrier -- was measured for the
     // single-FoV tail: first barrier at 4.5 K instead of 5.2 K cycles, but the
     // taps 6.9 K instead of 5.8 K: profiles/r02_wg_timeline.txt)
-    conv32d_body<KIND, ADD_SKIP, kPieces, HEAD, TNT, kRows, 2, FLOW>(
-        a, a.L, item, mp.n_main * kMChunk + c * (32 * TNT), item * slots + mp.n_main + c,
-        mp.taoff, item == 0 && c == 0 && a.dbg_wgs == 2);
-  }
-  stamp_workgroup(a, a.L, t0);
-}
-
-// mfma_products = 1: conv32mt_kernel's map of workgroups, main and tail bodies with the
-// one product (no FLOW form; its own name, as conv32m1_kernel)
-template <int KIND, bool ADD_SKIP, bool HEAD, int TNT>
-__global__ __launch_bounds__(kDThreads, 2) void conv32mt1_kernel(ConvDArgs a,
-                                                                 ConvTailMap mp) {
-  const int xcd = blockIdx.x & 7;
-  const int idx = blockIdx.x >> 3;
-  int item, r;
-  bool main_wg;
-  if (TNT == 1) {
-    const int per_item = mp.mains_per_xcd + mp.tails_per_xcd;
-    item = idx / per_item;
-    r = idx - item * per_item;
-    main_wg = r < mp.mains_per_xcd;
-    if (!main_wg) r -= mp.mains_per_xcd;
-  } else {
-    const int tails = mp.n * mp.tails_per_xcd;
-    main_wg = idx >= tails;
-    const int i2 = main_wg ? idx - tails : idx;
-    const int per = main_wg ? mp.mains_per_xcd : mp.tails_per_xcd;
-    item = i2 / per;
-    r = i2 - item * per;
-  }
-  if (item >= mp.n) return;
-  const long long t0 = a.dbg_wgs ? wall_clock64() : 0;
-  const int slots = mp.n_main + mp.n_tail;
-  if (main_wg) {
-    const int c = xcd * mp.mains_per_xcd + r;
-    if (c >= mp.n_main) return;
-    conv32m_body<KIND, ADD_SKIP, HEAD, false, false, 1>(
-        a, a.L, item, c * kMChunk, item * slots + c, blockIdx.x == 0 && a.dbg_wgs != 2);
-  } else {
-    const int c = xcd * mp.tails_per_xcd + r;
-    if (c >= mp.n_tail) return;
-    constexpr int kPieces = TNT == 1 ? kTPieces : kT3Pieces;
-    constexpr int kRows = TNT == 1 ? kTRows : kT3Rows;
-    conv32d_body<KIND, ADD_SKIP, kPieces, HEAD, TNT, kRows, 2, false, 1>(
+    conv32d_body<KIND, ADD_SKIP, kPieces, HEAD, TNT, kRows, 2, FLOW, PRODUCTS>(
         a, a.L, item, mp.n_main * kMChunk + c * (32 * TNT), item * slots + mp.n_main + c,
         mp.taoff, item == 0 && c == 0 && a.dbg_wgs == 2);
   }

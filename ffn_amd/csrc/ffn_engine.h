@@ -1,6 +1,7 @@
 // The engine and the canvas as the engine's own translation units see them (not part
 // of the C-ABI, no kernel in here):
-//   ffn_hip.hip      the engine, the conv launchers, the FoV step, the segment loop
+//   ffn_hip.hip      the engine, the FoV step, the segment loop
+//   ffn_stack*.hip   the conv launch layer (ffn_stack.h): run_stack and the kernel families
 //   ffn_canvas.hip   everything a canvas does between steps
 //   ffn_options.hip  options, profiler, debug readers (host code only)
 // A helper that more than one of them calls is declared here and defined once.
@@ -118,7 +119,7 @@ struct ffn_engine {
   // The resident stack and the fused step launch exist twice: the production form, and the
   // LAB form that carries the lab's plumbing (debug_clock, debug_layer, flow_debug,
   // debug_fused_trace, the flow trace).  flow_lab 0: the LAB form where one of those is on
-  // (lab_wanted, ffn_hip.hip); 1: always.
+  // (lab_wanted, ffn_stack_resident.hip); 1: always.
   int flow_lab = 0;
   long stat_lab_launches = 0;      // resident stacks queued in the LAB form
   // The resident launch needs every one of its workgroups on the chip at once.
@@ -483,9 +484,8 @@ inline int grid_for(long total, int block = 256) {
 // --- defined once, called across the units ---
 // ffn_hip.hip: the step ffn_canvas_segment_many_carry left in flight -- wait for it and
 // hand its results to the loops of its canvases (`only`: nothing to do unless that canvas
-// is one of them; callers hold neither `mu` nor `many_mu`); the change of conv_variant
+// is one of them; callers hold neither `mu` nor `many_mu`)
 int resolve_many_carry(ffn_engine* e, const ffn_canvas* only = nullptr);
-int switch_variant(ffn_engine* e, int value);
 // ffn_canvas.hip: the utility calls' scratch and the segment turn's (under util_mu)
 int ensure_scratch(ffn_engine* e, size_t bytes);
 int ensure_turn(ffn_engine* e, size_t n, size_t hist_n, size_t novl);

@@ -5,13 +5,13 @@
 // (image / seed / segmentation of a whole subvolume) are device resident.
 // The reference interfaces each entry point replaces are cited in the header.
 //
-// This unit: the engine itself (create, destroy, weights, the pace tuner), every conv
-// launcher and run_stack, the stateless predict calls, the FoV step (submit, wait) and
-// the segment loop that drives it.  What a canvas does between steps is ffn_canvas.hip;
-// options, profiler and debug readers are ffn_options.hip (ffn_engine.h).
+// This unit: the engine itself (create, destroy, weights, the pace tuner), the stateless
+// predict calls, the FoV step (submit, wait) and the segment loop that drives it.  The conv
+// stack they run is the launch layer behind ffn_stack.h (run_stack; no conv kernel is
+// named here).  What a canvas does between steps is ffn_canvas.hip; options, profiler and
+// debug readers are ffn_options.hip (ffn_engine.h).
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cmath>
@@ -25,12 +25,9 @@
 #include <vector>
 
 #include "ffn_engine.h"
+#include "ffn_stack.h"
 #include "ffn_kernels.h"
 #include "ffn_step_kernels.h"
-#include "ffn_conv_exact.h"
-#include "ffn_conv_split.h"
-#include "ffn_conv_resident.h"
-#include "ffn_conv_half.h"
 
 namespace {
 thread_local std::string g_error;
@@ -80,32 +77,6 @@ int flow_voided(ffn_engine* e, bool timed_out) {
               "launch per conv, same arithmetic)");
 }
 
-// Room for one more pair of profiler events: the recorded ones are flushed when fewer
-// than two are left (no allocation: the events were created with the engine).
-int event_pair(ffn_engine* e) {
-  return e->events_used + 2 > (int)e->events.size() ? flush_events(e) : FFN_OK;
-}
-
-// The event pair around ONE conv launch of a sampled stack (profiling mode 1).
-int prof_begin(ffn_engine* e) {
-  if (!e->prof_now) return FFN_OK;
-  if (int rc = event_pair(e)) return rc;
-  HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  return FFN_OK;
-}
-int prof_end(ffn_engine* e) {
-  if (e->prof_now) HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  return FFN_OK;
-}
-
-template <bool RI, bool RO, bool SK>
-int set_lds_attr(size_t bytes) {
-  HIP_TRY(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&conv32_kernel<RI, RO, SK>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return FFN_OK;
-}
-
 // x ~= hi + 2^-11 * res with hi, res fp16 (what the device does when staging)
 inline void split_fp16x2(float x, uint16_t part[2]) {
   const float xh = std::fabs(x) < 6.103515625e-05f ? 0.0f : x;
@@ -113,676 +84,6 @@ inline void split_fp16x2(float x, uint16_t part[2]) {
   const _Float16 res = (_Float16)((x - (float)hi) * 2048.0f);
   std::memcpy(&part[0], &hi, 2);
   std::memcpy(&part[1], &res, 2);
-}
-
-// The forms a split-product conv kernel is launched in: conv_a (KIND 0); conv_b (KIND 1)
-// without and with the residual (SK), each also with the head fused -- which the flagged
-// and the 80-voxel kernels have only with the residual.
-#define FFN_CONV_FORMS4(X) \
-  X(0, false, false); X(1, false, false); X(1, true, false); X(1, true, true)
-#define FFN_CONV_FORMS(X) FFN_CONV_FORMS4(X); X(1, false, true)
-#define FFN_LDS_ATTR(KERNEL, BYTES)                                           \
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL),          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
-
-int set_lds_attr_d(size_t bytes) {
-#define FFN_D8(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 8, HEADV>), bytes)
-#define FFN_D9(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 9, HEADV>), bytes)
-#define FFN_D10(KIND, SK, HEADV) FFN_LDS_ATTR((conv32d_kernel<KIND, SK, 10, HEADV>), bytes)
-  FFN_CONV_FORMS(FFN_D8);
-  FFN_CONV_FORMS(FFN_D9);
-  FFN_CONV_FORMS(FFN_D10);
-#undef FFN_D8
-#undef FFN_D9
-#undef FFN_D10
-  return FFN_OK;
-}
-
-int set_lds_attr_m() {
-#define FFN_M(KIND, SK, HEADV) FFN_LDS_ATTR((conv32m_kernel<KIND, SK, HEADV>), kMLdsBytes)
-#define FFN_MT(KIND, SK, HEADV)                                          \
-  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 1>), kMLdsBytes);       \
-  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 3>), kMLdsBytes)
-#define FFN_MTF(KIND, SK, HEADV) \
-  FFN_LDS_ATTR((conv32mt_kernel<KIND, SK, HEADV, 1, true>), kMLdsBytes)
-#define FFN_H(KIND, SK, HEADV) FFN_LDS_ATTR((conv32h_kernel<KIND, SK, HEADV>), kHLdsBytes)
-#define FFN_M1(KIND, SK, HEADV)                                           \
-  FFN_LDS_ATTR((conv32m1_kernel<KIND, SK, HEADV>), kMLdsBytes);           \
-  FFN_LDS_ATTR((conv32mt1_kernel<KIND, SK, HEADV, 1>), kMLdsBytes);       \
-  FFN_LDS_ATTR((conv32mt1_kernel<KIND, SK, HEADV, 3>), kMLdsBytes)
-  FFN_CONV_FORMS(FFN_M);
-  FFN_CONV_FORMS(FFN_MT);
-  FFN_CONV_FORMS(FFN_M1);
-  FFN_CONV_FORMS4(FFN_MTF);
-  FFN_CONV_FORMS4(FFN_H);
-#undef FFN_M
-#undef FFN_MT
-#undef FFN_MTF
-#undef FFN_H
-#undef FFN_M1
-  FFN_LDS_ATTR(conv32hs_kernel, kHLdsBytes);
-  FFN_LDS_ATTR(conv32ps_kernel<true>, kMLdsBytes);
-  FFN_LDS_ATTR(conv32ps_kernel<false>, kMLdsBytes);
-  return FFN_OK;
-}
-
-int set_lds_attr_e(size_t bytes) {
-#define FFN_E(KIND, SK, HEADV) \
-  FFN_LDS_ATTR((conv32d_kernel<KIND, SK, kEPieces, HEADV, kETiles, kERows, 2>), bytes)
-  FFN_CONV_FORMS(FFN_E);
-#undef FFN_E
-  return FFN_OK;
-}
-
-template <bool RI, bool RO, bool SK, int DBG = 0>
-int set_lds_attr_c(size_t bytes) {
-  HIP_TRY(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&conv32c_kernel<RI, RO, SK, DBG, 8>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  if (DBG == 0)
-    HIP_TRY(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv32c_kernel<RI, RO, SK, 0, 9>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  if (DBG == 0 && SK) {  // the fused-head form of the last conv
-    HIP_TRY(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv32c_kernel<RI, RO, SK, 0, 8, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    HIP_TRY(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv32c_kernel<RI, RO, SK, 0, 9, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  }
-  return FFN_OK;
-}
-
-
-template <bool RI, bool RO, bool SK>
-int launch_conv32(ffn_engine* e, int n, const float* in, float* out,
-                  const float* skip, int layer) {
-  ConvArgs a;
-  a.in = in;
-  a.out = out;
-  a.skip = skip;
-  a.wpack = e->weights + e->wpack_off[layer];
-  a.bias = e->weights + e->bias_off[layer];
-  a.valid = e->valid;
-  a.act_stride = e->g.act_stride;
-  a.XS = e->g.XS;
-  a.plane = e->g.plane;
-  a.R = e->g.R;
-  a.nchunks = e->g.nchunks;
-  if (int rc = prof_begin(e)) return rc;
-  hipLaunchKernelGGL((conv32_kernel<RI, RO, SK>), dim3(n * e->g.nchunks),
-                     dim3(kConvThreads), e->caps.lds_bytes, e->stream, a);
-  return prof_end(e);
-}
-
-struct HeadFusion {
-  bool on = false;
-  float pad_value = 0.f, move_thr = 0.f;
-};
-HeadFusion head_fusion(bool on, float pad_value, float move_thr) {
-  HeadFusion hf;
-  hf.on = on;
-  hf.pad_value = pad_value;
-  hf.move_thr = move_thr;
-  return hf;
-}
-
-template <bool RI, bool RO, bool SK>
-int launch_conv32c(ffn_engine* e, int n, const float* in, float* out,
-                   const float* skip, int layer,
-                   const HeadFusion& head = HeadFusion()) {
-  ConvCArgs a;
-  a.in = in;
-  a.out = out;
-  a.skip = skip;
-  a.wpack = e->weights + e->wpack_off[layer];
-  a.bias = e->weights + e->bias_off[layer];
-  a.pidx = e->pidx;
-  a.act_stride = e->g.act_stride;
-  a.XS = e->g.XS;
-  a.plane = e->g.plane;
-  a.Rc = e->caps.Rc;
-  a.nchunks = e->caps.nchunks_c;
-  a.V = e->g.V;
-  a.fx = e->g.fx;
-  a.fyfx = e->g.fy * e->g.fx;
-  a.total_slots = n * e->caps.nchunks_c;
-  a.slots_per_xcd = (a.total_slots + 7) / 8;
-  a.nbytes = (unsigned)((size_t)e->g.nchunks * kChunk * kFeatures * sizeof(float));
-  a.store_policy = e->store_policy;
-  // clocks of ONE mid-stack launch (a conv_a: ReLU in and out, no residual)
-  a.dbg = (e->dbg_clock && layer == e->dbg_layer) ? e->d_dbg : nullptr;
-  a.head_w = e->weights + e->wl_off;
-  a.seed_raw = e->seed_raw;
-  a.logits = e->logits;
-  a.head_count = e->count;
-  a.pad_value = head.pad_value;
-  a.move_thr = head.move_thr;
-  if (int rc = prof_begin(e)) return rc;
-  const dim3 grid(8 * a.slots_per_xcd), block(kConvThreads);
-  a.range_flag = e->range_flag;
-  a.range_tag = e->range_tag;
-#define FFN_C_LAUNCH(...)                                                       \
-  hipLaunchKernelGGL((conv32c_kernel<__VA_ARGS__>), grid, block, e->caps.lds_bytes_c, \
-                     e->stream, a)
-  if (RI == false && RO == false && SK == true && e->ablate != 0 &&
-      e->caps.Rc == 256) {
-    switch (e->ablate) {  // issue-rate experiments (conv_b instantiation only)
-      case 8: FFN_C_LAUNCH(false, false, true, 8); break;
-      case 16: FFN_C_LAUNCH(false, false, true, 16); break;
-      case 24: FFN_C_LAUNCH(false, false, true, 24); break;
-      default:
-        return fail(FFN_ERR_ARG, "unsupported ablate mask %d for variant 2",
-                    e->ablate);
-    }
-  } else if (head.on) {
-    if (e->caps.Rc == 256) FFN_C_LAUNCH(RI, RO, SK, 0, 8, true);
-    else FFN_C_LAUNCH(RI, RO, SK, 0, 9, true);
-  } else if (e->caps.Rc == 256) {
-    FFN_C_LAUNCH(RI, RO, SK, 0, 8);
-  } else {
-    FFN_C_LAUNCH(RI, RO, SK, 0, 9);
-  }
-#undef FFN_C_LAUNCH
-  return prof_end(e);
-}
-
-// The split-plane layout of variant 6 and the f32 layout of the others keep their
-// zero padding in different bytes of the same allocations: re-zero on a change.
-// (declared in ffn_engine.h: the option setter calls it too)
-}  // namespace
-
-int switch_variant(ffn_engine* e, int value) {
-  if ((value >= 6) != (e->conv_variant >= 6)) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemsetAsync(e->act_base, 0,
-                           (size_t)3 * e->max_batch * e->g.act_stride * sizeof(float),
-                           e->stream));
-  }
-  e->conv_variant = value;
-  return FFN_OK;
-}
-
-namespace {
-
-// conv32d launch: KIND 0 conv_a (T' = split(relu(conv(X') + b))), KIND 1 conv_b
-// (X = conv(T') + b [+ X]; X' = split(relu(X))), or the fused head
-void conv32d_args(ffn_engine* e, const StackPlan& plan, int n, const float* raw_in,
-                  float* raw_out, int layer, const HeadFusion& head, ConvDArgs& a) {
-  const Geom& g = e->caps.gp;
-  const long positions = g.act_stride / kFeatures;
-  a.L.in_sp = reinterpret_cast<const char*>(raw_in) + (size_t)g.guard * 16;
-  a.L.out_sp = reinterpret_cast<char*>(raw_out) + (size_t)g.guard * 16;
-  a.x_f32 = e->rawX + (size_t)g.guard * 4;
-  a.L.wpack = reinterpret_cast<const char*>(e->wpackd + (size_t)layer * e->wpackd_layer);
-  a.L.bias = e->weights + e->bias_off[layer];
-  a.item_bytes = g.act_stride * (long)sizeof(float);
-  a.sp_plane_bytes = positions * 16;
-  a.XS = g.XS;
-  a.plane = g.plane;
-  // the chunks of a plain launch: conv32m's 128-voxel ones (MT and H bring their own
-  // maps and read conv32m's count), 96-voxel ones, or conv32d's 160-voxel ones
-  const bool small = plan.family == ConvFamily::D96;
-  const int nchunks = small ? e->caps.nchunks_e
-                      : plan.family == ConvFamily::D160 ? e->caps.nchunks_k
-                                                        : e->caps.nchunks_m;
-  a.nchunks = nchunks;
-  a.V = g.V;
-  a.fx = g.fx;
-  a.fyfx = g.fy * g.fx;
-  a.total_slots = n * nchunks;
-  a.slots_per_xcd = (a.total_slots + 7) / 8;
-  auto magic = [](int d) { return (unsigned)(((1ull << 32) + d - 1) / d); };
-  a.magic_nchunks = magic(nchunks);
-  a.magic_fyfx = magic(g.fy * g.fx);
-  a.magic_fx = magic(g.fx);
-  a.permuted = e->caps.permuted;
-  a.ds0 = g.dstr[0];
-  a.ds1 = g.dstr[1];
-  a.ds2 = g.dstr[2];
-  a.sp_bytes = (unsigned)((size_t)g.act_stride * sizeof(float) - (size_t)g.guard * 32);
-  std::memcpy(a.aoff, small ? e->caps.esched_aoff : e->caps.dsched_aoff, sizeof(a.aoff));
-  std::memcpy(a.btap, e->caps.dsched_btap, sizeof(a.btap));
-  a.L.dbg = (e->dbg_clock && layer == e->dbg_layer) ? e->d_dbg : nullptr;
-  a.dbg_wgs = e->dbg_clock == 2 ? 1 : e->dbg_clock == 3 ? 2 : 0;
-  a.head_w = e->weights + e->wl_off;
-  a.seed_raw = e->seed_raw;
-  a.logits = e->logits;
-  a.head_count = e->count;
-  a.pad_value = head.pad_value;
-  a.move_thr = head.move_thr;
-  a.range_flag = e->range_flag;
-  a.range_tag = e->range_tag;
-  a.flow_flags = e->flow_flags;
-  a.flow_n_main = e->caps.n_main;
-  a.flow_err = e->flow_err;
-  a.flow_halo = g.fy * g.fx + g.fx + 1;
-  a.flow_dbg = e->flow_debug;
-  a.flow_trace = e->dbg_clock == 4 ? e->flow_trace : nullptr;
-  a.L.layer = layer;
-  a.L.flow_wait_on = 0;
-  a.L.flow_wait = a.L.flow_set = 0;
-}
-
-void tail_map(const ffn_engine* e, int n, ConvTailMap& mp) {
-  const bool one = n == 1;
-  mp.n = n;
-  mp.n_main = e->caps.n_main;
-  mp.n_tail = one ? e->caps.n_tail : e->caps.n_tail3;
-  mp.mains_per_xcd = (mp.n_main + 7) / 8;
-  mp.tails_per_xcd = (mp.n_tail + 7) / 8;
-  std::memcpy(mp.taoff, one ? e->caps.tsched_aoff : e->caps.t3sched_aoff, sizeof(mp.taoff));
-}
-
-template <int KIND, bool SK>
-int launch_conv32d(ffn_engine* e, const StackPlan& plan, int n, const float* raw_in,
-                   float* raw_out, int layer, const HeadFusion& head = HeadFusion()) {
-  ConvDArgs a;
-  conv32d_args(e, plan, n, raw_in, raw_out, layer, head, a);
-  if (int rc = prof_begin(e)) return rc;
-  const dim3 grid(8 * a.slots_per_xcd), block(kDThreads);
-  const int ks = e->caps.Rc_k / 32;
-#define FFN_D_LAUNCH(KSV, HEADV)                                                 \
-  hipLaunchKernelGGL((conv32d_kernel<KIND, SK, KSV, HEADV>), grid, block,        \
-                     e->caps.lds_bytes_d, e->stream, a)
-#define FFN_E_LAUNCH(HEADV)                                                      \
-  hipLaunchKernelGGL(                                                            \
-      (conv32d_kernel<KIND, SK, kEPieces, HEADV, kETiles, kERows, 2>), grid,     \
-      block, e->caps.lds_bytes_e, e->stream, a)
-  if (plan.family == ConvFamily::MT) {
-    // one FoV: 32-voxel tail workgroups (balance over the CUs); several: the
-    // same voxels in 96-voxel ones (cost per voxel) -- the same bits
-    const bool one = plan.tail_tiles == 1;
-    ConvTailMap mp;
-    tail_map(e, n, mp);
-    const dim3 tgrid(8 * n * (mp.mains_per_xcd + mp.tails_per_xcd));
-    const bool one_product = plan.products == 1;  // (per-layer launches without FLOW)
-    const bool flow1 = one && e->flow == 1 && !one_product;
-    if (flow1) {
-      a.L.flow_wait_on = layer > 0;
-      a.L.flow_wait = e->flow_epoch;
-      a.L.flow_set = ++e->flow_epoch;
-    }
-#define FFN_MT_LAUNCH(HEADV)                                                      \
-  if (flow1) {                                                                    \
-    if constexpr (KIND == 0 || SK || !HEADV)                                      \
-      hipLaunchKernelGGL((conv32mt_kernel<KIND, SK, HEADV, 1, true>), tgrid,      \
-                         block, kMLdsBytes, e->stream, a, mp);                    \
-  } else if (one_product) {                                                       \
-    if (one)                                                                      \
-      hipLaunchKernelGGL((conv32mt1_kernel<KIND, SK, HEADV, 1>), tgrid, block,    \
-                         kMLdsBytes, e->stream, a, mp);                           \
-    else                                                                          \
-      hipLaunchKernelGGL((conv32mt1_kernel<KIND, SK, HEADV, 3>), tgrid, block,    \
-                         kMLdsBytes, e->stream, a, mp);                           \
-  } else if (one)                                                                 \
-    hipLaunchKernelGGL((conv32mt_kernel<KIND, SK, HEADV, 1>), tgrid, block,       \
-                       kMLdsBytes, e->stream, a, mp);                             \
-  else                                                                            \
-    hipLaunchKernelGGL((conv32mt_kernel<KIND, SK, HEADV, 3>), tgrid, block,       \
-                       kMLdsBytes, e->stream, a, mp)
-    if (head.on) {
-      if constexpr (KIND == 1) { FFN_MT_LAUNCH(true); }
-    } else {
-      FFN_MT_LAUNCH(false);
-    }
-#undef FFN_MT_LAUNCH
-  } else if (plan.family == ConvFamily::M) {
-#define FFN_M_LAUNCH(HEADV)                                                      \
-  if (plan.products == 1)                                                        \
-    hipLaunchKernelGGL((conv32m1_kernel<KIND, SK, HEADV>), grid, block,          \
-                       kMLdsBytes, e->stream, a);                                \
-  else                                                                           \
-    hipLaunchKernelGGL((conv32m_kernel<KIND, SK, HEADV>), grid, block,           \
-                       kMLdsBytes, e->stream, a)
-    if (head.on) {
-      if constexpr (KIND == 1) { FFN_M_LAUNCH(true); }
-    } else {
-      FFN_M_LAUNCH(false);
-    }
-#undef FFN_M_LAUNCH
-  } else if (plan.family == ConvFamily::D96) {
-    if (head.on) {
-      if constexpr (KIND == 1) FFN_E_LAUNCH(true);
-    } else {
-      FFN_E_LAUNCH(false);
-    }
-  } else if (head.on) {
-    if constexpr (KIND == 1) {
-      if (ks == 8) FFN_D_LAUNCH(8, true);
-      else if (ks == 9) FFN_D_LAUNCH(9, true);
-      else FFN_D_LAUNCH(10, true);
-    }
-  } else {
-    if (ks == 8) FFN_D_LAUNCH(8, false);
-    else if (ks == 9) FFN_D_LAUNCH(9, false);
-    else FFN_D_LAUNCH(10, false);
-  }
-#undef FFN_D_LAUNCH
-#undef FFN_E_LAUNCH
-  return prof_end(e);
-}
-
-// FoVs described by `si` -> logits (+ count of logits >= move_thr, + seed_raw)
-// conv0_a of a step whose range tag is `tag` (sp.n > 0: a speculative launch)
-// conv0_a of the split-product family as the argument block of the fused launch;
-// returns its number of tiles.  next: for the step AFTER the current one (its
-// outputs go to the other set: ffn_engine::seed_raw_alt ...)
-int conv0a_split_args(ffn_engine* e, float pad_value, unsigned tag, const SpecArgs& sp,
-                      bool next, Conv0Next& nx) {
-  const float* W = e->weights;
-  const Geom& q = e->caps.gp;  // the split-product kernels' layout of the FoV
-  const int qz = (q.fz + kC0Z - 1) / kC0Z, qy = (q.fy + kC0Y - 1) / kC0Y,
-            qx = (q.fx + kC0X - 1) / kC0X;
-  nx.pad_value = pad_value;
-  nx.w = W + (e->caps.permuted ? e->w0ap_off : e->w0a_off);
-  nx.bias = W + e->b0a_off;
-  nx.out = e->bufT;
-  nx.seed_raw = next ? e->seed_raw_alt : e->seed_raw;
-  nx.q = q;
-  nx.tiles_y = qy;
-  nx.tiles_x = qx;
-  nx.so.out_sp = reinterpret_cast<char*>(e->rawT) + (size_t)q.guard * 16;
-  nx.so.sp_plane_bytes = (q.act_stride / kFeatures) * 16;
-  nx.so.item_bytes = q.act_stride * (long)sizeof(float);
-  nx.so.range_flag = next ? e->range_flag_alt : e->range_flag;
-  nx.so.range_tag = tag;
-  nx.sp = sp;
-  if (sp.n > 0) nx.sp.choice = next ? e->d_spec_choice_alt : e->d_spec_choice;
-  return qz * qy * qx;
-}
-
-void launch_conv0a(ffn_engine* e, int n, const StepItems& si, float pad_value,
-                   unsigned tag, const SpecArgs& sp, bool next = false) {
-  const Geom& g = e->g;
-  const float* W = e->weights;
-  const int tz = (g.fz + kC0Z - 1) / kC0Z, ty = (g.fy + kC0Y - 1) / kC0Y,
-            tx = (g.fx + kC0X - 1) / kC0X;
-  if (e->conv_variant >= 6) {
-    Conv0Next nx;
-    const int tiles = conv0a_split_args(e, pad_value, tag, sp, next, nx);
-    hipLaunchKernelGGL(conv0a_mfma_kernel<true>, dim3(tiles, n),
-                       dim3(kC0Threads), 0, e->stream, si, pad_value, nx.w, nx.bias,
-                       nx.out, nx.seed_raw, nx.q, nx.tiles_y, nx.tiles_x, nx.so, nx.sp);
-  } else {
-    SpecArgs sp2 = sp;
-    if (sp.n > 0) sp2.choice = next ? e->d_spec_choice_alt : e->d_spec_choice;
-    hipLaunchKernelGGL(conv0a_mfma_kernel<false>, dim3(tz * ty * tx, n),
-                       dim3(kC0Threads), 0, e->stream, si, pad_value,
-                       W + e->w0a_off, W + e->b0a_off, e->bufT,
-                       next ? e->seed_raw_alt : e->seed_raw, g, ty, tx,
-                       Conv0SplitOut(), sp2);
-  }
-}
-
-// What a resident launch of the whole stack adds to a conv's arguments: where the layers'
-// planes, weight fragments (wpack: conv32d's or conv32h's packing) and biases are, its
-// epochs, its beat (auto_pace: the one to run at where the user set none).  An ordinary
-// launch: nothing stamped, nothing ahead.
-void stack_tab(ffn_engine* e, const uint16_t* wpack, int auto_pace, ConvStackTab* tb) {
-  const Geom& g = e->caps.gp;
-  tb->nlayers = 2 * e->depth - 1;
-  tb->dbg_layer = e->dbg_layer;
-  tb->sp_t = reinterpret_cast<const char*>(e->rawT) + (size_t)g.guard * 16;
-  tb->sp_s = reinterpret_cast<char*>(e->rawS) + (size_t)g.guard * 16;
-  tb->wpack0 = reinterpret_cast<const char*>(wpack);
-  tb->wpack_stride = (long)(e->wpackd_layer * sizeof(uint16_t));
-  tb->bias0 = e->weights + e->bias_off[0];
-  tb->bias_stride = e->depth > 1 ? (long)(e->bias_off[1] - e->bias_off[0]) : 0;
-  tb->epoch0 = e->flow_epoch;
-  e->flow_epoch += (unsigned)tb->nlayers;
-  tb->l_begin = 0;
-  tb->l_end = tb->nlayers;
-  tb->pace = e->flow_pace < 0 ? auto_pace : e->flow_pace;
-  tb->pace_tail = 0;
-  tb->pace_spread = e->flow_pace_spread < 0 ? tb->pace : e->flow_pace_spread;
-  tb->stamps = nullptr;
-  tb->ahead_choice = nullptr;
-  tb->trace = 0;
-}
-
-// Whether the launches of a step take their LAB form: one of the lab's run-time options is
-// on (the production forms have no code for them), the build is an experiment or ablation
-// build, or engine option flow_lab asks for it.  (debug_fused_trace is per launch: a
-// launch that stamps is a LAB launch, launch_conv32ps and the fused step launch.)
-bool lab_wanted(const ffn_engine* e) {
-  return e->flow_lab != 0 || kExp || kAbl != 0 || FFN_FLOW_TRACE != 0 || e->dbg_clock != 0 ||
-         e->dbg_layer != kDbgLayerDefault || e->flow_debug != 0;
-}
-
-// The 2 depth - 1 convs of ONE FoV as a single resident launch (conv32ps,
-// ffn_conv_resident.h): conv32mt's workgroups keep their voxels through the stack and
-// hand rows to each other through the tile words instead of kernel boundaries.
-// ev0 / ev1: a sampled launch -- the events carry the START and END of this very dispatch
-// (hipExtLaunchKernelGGL: the timestamps rocprofv3 reads), not markers queued around it: a
-// marker is a barrier packet with system-scope fences of its own, 2 - 3 us each, which the
-// sampled launch and the step around it would wait behind
-int launch_conv32ps(ffn_engine* e, const StackPlan& plan, float pad_value, float move_thr,
-                    const int* ahead_choice = nullptr, hipEvent_t ev0 = nullptr,
-                    hipEvent_t ev1 = nullptr) {
-  ConvDArgs a;
-  conv32d_args(e, plan, 1, e->rawT, e->rawS, 0, head_fusion(true, pad_value, move_thr), a);
-  a.L.dbg = e->dbg_clock ? e->d_dbg : nullptr;
-  ConvTailMap mp;
-  tail_map(e, 1, mp);
-  ConvStackTab tb;
-  stack_tab(e, e->wpackd, e->pace_auto, &tb);
-  tb.pace_tail = e->flow_pace_tail;
-  const dim3 grid(8 * (mp.mains_per_xcd + mp.tails_per_xcd)), block(kDThreads);
-  tb.stamps = e->d_stamps;
-  tb.ahead_choice = ahead_choice;
-  // (2: the stack in front of the traced step, queued ahead one call earlier: its end only)
-  tb.trace = e->trace_now ? 1 : (ahead_choice && e->fused_trace_in == 1) ? 2 : 0;
-  const long long t_l0 = e->t_arrived_ns ? steady_ns() : 0;
-  if (lab_wanted(e) || tb.trace != 0) {
-    e->stat_lab_launches += 1;
-    if (ev0)
-      hipExtLaunchKernelGGL(conv32ps_kernel<true>, grid, block, kMLdsBytes, e->stream, ev0, ev1,
-                            0, a, mp, tb);
-    else
-      hipLaunchKernelGGL(conv32ps_kernel<true>, grid, block, kMLdsBytes, e->stream, a, mp, tb);
-  } else {
-    const ConvDArgsLean al = lean_args(a);
-    const ConvStackTabLean tl = lean_tab(tb);
-    if (ev0)
-      hipExtLaunchKernelGGL(conv32ps_kernel<false>, grid, block, kMLdsBytes, e->stream, ev0, ev1,
-                            0, al, mp, tl);
-    else
-      hipLaunchKernelGGL(conv32ps_kernel<false>, grid, block, kMLdsBytes, e->stream, al, mp, tl);
-  }
-  if (e->t_arrived_ns) {
-    const long long t_l1 = steady_ns();
-    if (t_l1 - e->t_arrived_ns < 100000) {  // (inside a segment: see ConvStackTab::stamps)
-      e->stat_turn_host_ns += t_l1 - e->t_arrived_ns;
-      e->stat_launch_host_ns += t_l1 - t_l0;
-      e->stat_turn_host_count += 1;
-    }
-    e->t_arrived_ns = 0;
-  }
-  return FFN_OK;
-}
-
-// The same stack on 64-voxel workgroups, two per CU (conv32hs, ffn_conv_half.h).
-void half_map(const ffn_engine* e, ConvHalfMap& mp) {
-  // (the dispatcher hands an XCD's first blocks to its empty CUs: cus / 8 first slots)
-  mp.n_chunks = e->caps.n_half;
-  mp.per_first = std::max(1, e->cus / 8);
-  mp.n_first = std::min(e->caps.n_half, 8 * mp.per_first);
-  mp.per_second = (e->caps.n_half - mp.n_first + 7) / 8;
-}
-
-// one conv of the 80-voxel family as its own launch: what a resident step that came
-// back void is repeated with (the same bits), and flow = 0
-template <int KIND, bool SK>
-int launch_conv32h(ffn_engine* e, const StackPlan& plan, const float* raw_in, float* raw_out,
-                   int layer, const HeadFusion& head = HeadFusion()) {
-  ConvDArgs a;
-  conv32d_args(e, plan, 1, raw_in, raw_out, layer, head, a);
-  a.L.wpack = reinterpret_cast<const char*>(e->wpackh + (size_t)layer * e->wpackd_layer);
-  a.flow_n_main = -1;
-  ConvHalfMap mp;
-  half_map(e, mp);
-  const dim3 grid(8 * (mp.per_first + mp.per_second)), block(kDThreads);
-  if (head.on) {
-    if constexpr (KIND == 1)
-      hipLaunchKernelGGL((conv32h_kernel<KIND, SK, true>), grid, block, kHLdsBytes, e->stream,
-                         a, mp);
-  } else {
-    hipLaunchKernelGGL((conv32h_kernel<KIND, SK, false>), grid, block, kHLdsBytes, e->stream,
-                       a, mp);
-  }
-  return FFN_OK;
-}
-
-int launch_conv32hs(ffn_engine* e, const StackPlan& plan, float pad_value, float move_thr) {
-  ConvDArgs a;
-  conv32d_args(e, plan, 1, e->rawT, e->rawS, 0, head_fusion(true, pad_value, move_thr), a);
-  a.flow_n_main = -1;
-  ConvHalfMap mp;
-  half_map(e, mp);
-  ConvStackTab tb;
-  stack_tab(e, e->wpackh, 0, &tb);  // (no measured beat for this family)
-  const dim3 grid(8 * (mp.per_first + mp.per_second)), block(kDThreads);
-  hipLaunchKernelGGL(conv32hs_kernel, grid, block, kHLdsBytes, e->stream, a, mp, tb);
-  return FFN_OK;
-}
-
-// The plan of a stack of n FoVs as the engine's options stand (flow_skip: the engine's,
-// or 0 for "once no repeat is pending").
-StackPlan plan_for(const ffn_engine* e, int n, int flow_skip) {
-  return plan_stack(e->caps, e->conv_variant, e->flow, flow_skip, e->tail_batched,
-                    e->batch_chunks, n, e->mfma_products);
-}
-
-// The chain of launches of a stack, one per conv: conv0_b, then per residual module
-// conv_a (layer 2 i - 1) and conv_b (layer 2 i; last: the one that may take the head).
-template <class First, class A, class B>
-int walk_stack(int depth, First first, A conv_a, B conv_b) {
-  int rc = first();
-  for (int i = 1; i < depth && !rc; ++i) {
-    rc = conv_a(2 * i - 1);
-    if (!rc) rc = conv_b(2 * i, i == depth - 1);
-  }
-  return rc;
-}
-
-// conv0a_done: the step's conv0_a has been queued already (a speculative launch
-// that chose its position)
-// ahead: the stack of the step AFTER the one being submitted, behind the speculative
-// conv0_a just queued for it (engine option stack_ahead; conv0a_done with it)
-int run_stack(ffn_engine* e, int n, const StepItems& si, float pad_value,
-              float move_thr, bool conv0a_done = false, bool ahead = false) {
-  const Geom& g = e->g;
-  const float* W = e->weights;
-  if (!conv0a_done) drop_spec(e);
-  if (e->ahead_valid) e->stat_ahead_wasted += 1;  // (a caller that steps past it)
-  e->spec.valid = false;
-  e->ahead_valid = false;
-  e->last_stack_resident = false;
-  e->range_tag = next_tag(e->range_tag);
-  // this step's set of conv0_a outputs: what a launch made ahead for it wrote,
-  // what its own conv0_a (below) writes
-  std::swap(e->seed_raw, e->seed_raw_alt);
-  std::swap(e->range_flag, e->range_flag_alt);
-  std::swap(e->d_spec_choice, e->d_spec_choice_alt);
-  const bool sampled = (e->stack_calls % e->prof_every) == 0;
-  e->stack_calls++;
-  e->prof_now = e->prof_mode == 1 && sampled;
-  const bool prof_chain = e->prof_mode == 2 && sampled;
-  if (!conv0a_done) launch_conv0a(e, n, si, pad_value, e->range_tag, SpecArgs());
-  bool head_fused = false;
-  e->ahead_ev_pending = false;
-  const StackPlan plan = plan_for(e, n, e->flow_skip);
-  if ((plan.family == ConvFamily::MT || plan.family == ConvFamily::H) && n == 1 &&
-      e->flow == 2 && e->flow_skip > 0)
-    e->flow_skip -= 1;  // the repeat of a voided resident step: per-layer launches
-  // a sampled stack that runs as ONE resident launch is timed by that dispatch's own
-  // start / end (launch_conv32ps); a chain of launches by markers around it (and so is
-  // conv32hs, and the resident launch of an engine with tail_batched set)
-  const bool one_launch = resident_mt(plan) && e->tail_batched == 0;
-  hipEvent_t k_ev0 = nullptr, k_ev1 = nullptr;
-  if (prof_chain && ahead) {
-    if (one_launch) k_ev0 = e->ahead_ev[0], k_ev1 = e->ahead_ev[1];
-    else HIP_TRY(hipEventRecord(e->ahead_ev[0], e->stream));
-  } else if (prof_chain) {
-    if (int rc = event_pair(e)) return rc;
-    e->chain_launches_pending.push_back(2 * e->depth - 1);
-    if (one_launch) {
-      k_ev0 = e->events[e->events_used], k_ev1 = e->events[e->events_used + 1];
-      e->events_used += 2;
-    } else {
-      HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-    }
-  }
-  int rc;
-  if (e->conv_variant >= 6 && e->depth == 1)
-    return fail(FFN_ERR_ARG, "conv_variant 6 needs depth >= 2 (fused head)");
-  if (ahead && !resident_mt(plan))
-    return fail(FFN_ERR_STATE, "stack_ahead without the resident launch");
-  // the split-product families: T' -> (X, X') -> T' -> ... ; the head is always fused
-  // into the last conv_b
-  const auto head = [&](bool on) { return head_fusion(on, pad_value, move_thr); };
-  e->last_stack_resident = plan.resident;
-  if (plan.resident) {
-    rc = plan.family == ConvFamily::H
-             ? launch_conv32hs(e, plan, pad_value, move_thr)
-             : launch_conv32ps(e, plan, pad_value, move_thr,
-                               ahead ? e->d_spec_choice : nullptr, k_ev0, k_ev1);
-    head_fused = true;
-  } else if (plan.family == ConvFamily::H) {
-    rc = walk_stack(
-        e->depth, [&] { return launch_conv32h<1, false>(e, plan, e->rawT, e->rawS, 0); },
-        [&](int l) { return launch_conv32h<0, false>(e, plan, e->rawS, e->rawT, l); },
-        [&](int l, bool last) {
-          return launch_conv32h<1, true>(e, plan, e->rawT, e->rawS, l, head(last));
-        });
-    head_fused = true;
-  } else if (e->conv_variant >= 6) {
-    rc = walk_stack(
-        e->depth, [&] { return launch_conv32d<1, false>(e, plan, n, e->rawT, e->rawS, 0); },
-        [&](int l) { return launch_conv32d<0, false>(e, plan, n, e->rawS, e->rawT, l); },
-        [&](int l, bool last) {
-          return launch_conv32d<1, true>(e, plan, n, e->rawT, e->rawS, l, head(last));
-        });
-    head_fused = true;
-  } else if (plan.family == ConvFamily::Conv32) {
-    rc = walk_stack(
-        e->depth,
-        [&] { return launch_conv32<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0); },
-        [&](int l) { return launch_conv32<true, true, false>(e, n, e->bufX, e->bufT, nullptr, l); },
-        [&](int l, bool) {
-          return launch_conv32<false, false, true>(e, n, e->bufT, e->bufX, e->bufX, l);
-        });
-  } else {
-    // conv_variant 2: T is post-ReLU (conv0_a / conv_a apply it), X is the raw
-    // residual stream
-    rc = walk_stack(
-        e->depth,
-        [&] { return launch_conv32c<false, false, false>(e, n, e->bufT, e->bufX, nullptr, 0); },
-        [&](int l) {
-          return launch_conv32c<true, true, false>(e, n, e->bufX, e->bufT, nullptr, l);
-        },
-        [&](int l, bool last) {
-          head_fused = e->fuse_head && last && e->ablate == 0;
-          return launch_conv32c<false, false, true>(e, n, e->bufT, e->bufX, e->bufX, l,
-                                                    head(head_fused));
-        });
-  }
-  if (rc) return rc;
-  if (prof_chain && ahead) {
-    if (!k_ev0) HIP_TRY(hipEventRecord(e->ahead_ev[1], e->stream));
-    e->ahead_ev_pending = true;
-  } else if (prof_chain && !k_ev0) {
-    HIP_TRY(hipEventRecord(e->events[e->events_used++], e->stream));
-  }
-  e->count_blocks = head_fused ? plan.chunks : kHeadBlocks;
-  if (!head_fused)
-    hipLaunchKernelGGL(head_kernel, dim3(kHeadBlocks, n), dim3(256), 0, e->stream,
-                       e->bufX, e->seed_raw, pad_value, W + e->wl_off, move_thr,
-                       e->logits, e->count, g);
-  HIP_TRY(hipGetLastError());
-  return FFN_OK;
 }
 
 // Step descriptors for the dense uploaded FoVs (predict / forward_resident):
@@ -983,34 +284,13 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
   // The residency halves of flow_fits and h_ok: what the geometry allows
   // (ffn_stack_plan.h) and THIS device can hold.
   E_TRY(hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id));
-  if (caps.t_ok && depth >= 2) {
-    // a single-FoV step of conv32mt runs its convs as ONE resident launch --
-    // where the device can hold all of its workgroups at once: they wait for
-    // each other, so one that is not on the chip stalls the rest until their
-    // polls give up (a partitioned device, fewer CUs than main chunks)
-    // (both forms of the kernel: the smaller occupancy decides)
-    int per_cu = 0, per_cu_lab = 0;
-    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
-    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32ps_kernel<false>,
-                                                       kDThreads, kMLdsBytes));
-    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32ps_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kMLdsBytes));
-    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_lab, conv32ps_kernel<true>,
-                                                       kDThreads, kMLdsBytes));
-    per_cu = std::min(per_cu, per_cu_lab);
-    ConvTailMap mp;
-    tail_map(e, 1, mp);
-    const int grid = 8 * (mp.mains_per_xcd + mp.tails_per_xcd);
-    e->flow_fits = e->cus >= caps.n_main && (long)e->cus * per_cu >= grid;
-    // conv32hs (variant 10): 80-voxel workgroups, two per CU, all resident at once
-    E_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(conv32hs_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kHLdsBytes));
-    E_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv32hs_kernel, kDThreads,
-                                                       kHLdsBytes));
-    ConvHalfMap hm;
-    half_map(e, hm);
-    e->h_ok = caps.h_geom_ok && (long)e->cus * per_cu >= 8 * (hm.per_first + hm.per_second);
+  // (the attributes first: the occupancy a resident kernel is asked for is the one it has
+  // with its LDS granted)
+  int rc_stack = set_stack_lds_attrs(e);
+  if (!rc_stack) rc_stack = stack_residency(e);
+  if (rc_stack) {
+    ffn_engine_destroy(e);
+    return rc_stack;
   }
   e->flow = e->flow_fits ? 2 : 0;
 
@@ -1069,28 +349,6 @@ int ffn_engine_create(int device_id, const int32_t fov_zyx[3],
   for (auto& ev : e->events) E_TRY(hipEventCreate(&ev));
   for (auto& ev : e->ahead_ev) E_TRY(hipEventCreate(&ev));
 
-  {
-    int rc = set_lds_attr<false, false, false>(caps.lds_bytes);
-    if (!rc) rc = set_lds_attr<true, true, false>(caps.lds_bytes);
-    if (!rc) rc = set_lds_attr<false, false, true>(caps.lds_bytes);
-    // conv32c only where it takes the FoV (set_conv_variant refuses 2 elsewhere): rows past
-    // 119 voxels put lds_bytes_c beyond what a workgroup may ask for, and asking failed
-    // the creation of an engine that conv32 and the split-product kernels can serve
-    const bool c_ok = caps.exact_variant == 2;
-    if (!rc && c_ok) rc = set_lds_attr_c<false, false, false>(caps.lds_bytes_c);
-    if (!rc && c_ok) rc = set_lds_attr_c<true, true, false>(caps.lds_bytes_c);
-    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true>(caps.lds_bytes_c);
-    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 8>(caps.lds_bytes_c);
-    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 16>(caps.lds_bytes_c);
-    if (!rc && c_ok) rc = set_lds_attr_c<false, false, true, 24>(caps.lds_bytes_c);
-    if (!rc && caps.d_ok) rc = set_lds_attr_d(caps.lds_bytes_d);
-    if (!rc && caps.e_ok) rc = set_lds_attr_e(caps.lds_bytes_e);
-    if (!rc && caps.m_ok) rc = set_lds_attr_m();
-    if (rc) {
-      ffn_engine_destroy(e);
-      return rc;
-    }
-  }
 #undef E_TRY
   *out = e;
   return FFN_OK;

@@ -2,16 +2,27 @@
 // plain types (ffn_types.h: the activation layout is described there) and the small
 // device helpers below.
 //
-// The kernel headers define non-template __global__ functions, so each of them is
-// included by exactly ONE translation unit, behind this header:
-//   ffn_hip.hip     ffn_step_kernels.h    conv0_a in front of the stack; head, faces, paste
-//                   ffn_conv_exact.h      conv_variant 0, 2: exact f32
-//                   ffn_conv_split.h      conv_variant 6 .. 9: fp16 split products, FLOW
-//                   ffn_conv_resident.h   conv32ps: the stack as one launch
-//                   ffn_conv_half.h       conv32h / conv32hs: two chains per SIMD
-//                   (in this order: each builds on the ones above it)
-//   ffn_canvas.hip  ffn_canvas_kernels.h  box I/O, commit, segment turn
-//                   ffn_restrict_kernels.h  MovementRestrictor planes
+// A kernel header that defines a non-template __global__ function is included by exactly
+// ONE translation unit; one that holds templates and __forceinline__ device code only (T)
+// by every unit that needs it.  Without relocatable device code a unit that instantiates
+// a kernel gets its own device copy of it, so each kernel form is instantiated -- launched,
+// given its attributes, asked for its occupancy -- in one unit alone.  All behind this
+// header:
+//   ffn_conv0a.h (T)        conv0_a in front of the stack: ffn_stack.hip launches its
+//                           kernel, the fused step launch of ffn_hip.hip runs its body
+//   ffn_hip.hip             ffn_step_kernels.h    faces, paste, the fused step launches
+//   ffn_stack.hip           ffn_conv_exact.h      conv_variant 0, 2: exact f32; the head
+//   the conv launch layer   ffn_conv_split.h (T)     conv_variant 6 .. 9: fp16 split
+//   (ffn_stack_units.h)                              products, FLOW; conv32d's forms are
+//                                                    ffn_stack_d.hip's, conv32m / mt's
+//                                                    ffn_stack_m.hip's
+//                           ffn_conv_resident.h (T)  conv32ps, the stack as one launch:
+//                                                    ffn_stack_resident.hip
+//                           (in this order: each builds on the one above it)
+//   ffn_stack_resident.hip  ffn_conv_half.h       conv32h / conv32hs: two chains per SIMD
+//                                                 (behind the two above)
+//   ffn_canvas.hip          ffn_canvas_kernels.h  box I/O, commit, segment turn
+//                           ffn_restrict_kernels.h  MovementRestrictor planes
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,6 +35,13 @@
 namespace ffn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// (global address space spelled out: through generic pointers these would be flat
+// loads, which the compiler orders against every LDS access)
+#define FFN_GLOBAL __attribute__((address_space(1)))
 
 __device__ __forceinline__ bool in_pred_box(const Geom& g, int z, int y, int x) {
   return z >= g.c0[0] && z < g.c1[0] && y >= g.c0[1] && y < g.c1[1] && x >= g.c0[2] &&

@@ -10,6 +10,7 @@
 #include <map>
 
 #include "ffn_engine.h"
+#include "ffn_stack.h"
 
 // Flush the per-launch event pairs recorded since the last flush.
 int flush_events(ffn_engine* e) {

@@ -38,6 +38,8 @@ constexpr int kCLdsStride = 40;      // LDS row stride in floats: 32 channels + 
 constexpr int kDChunk = 160;
 constexpr int kDThreads = 256;
 constexpr int kDRowB = 144;          // epilogue: row stride of the partial sums in LDS
+constexpr int kDTaps = 28;           // taps of a layer's packed weights: 27 + the all-zero tap
+constexpr int kFlowStride = 64;      // FLOW hand-off: words between two producers' words
 constexpr int kERows = 208, kETiles = 3, kEPieces = 7;
 // conv32m
 constexpr int kMChunk = 128;
@@ -95,7 +97,7 @@ struct StepItem {
   ffn_step_request req;
 };
 
-// positions a speculative conv0_a launch looks at (SpecArgs, ffn_step_kernels.h)
+// positions a speculative conv0_a launch looks at (SpecArgs, ffn_conv0a.h)
 constexpr int kSpecMax = 3;
 
 // the segment turn (ffn_canvas_kernels.h): grid cap of its sweeps = partial sums per

@@ -13,7 +13,7 @@ by at least g.
 
 The split-product kernels (conv_variant 6 .. 10) add one condition.  They carry an f32
 value v as two fp16 numbers (split8_fp16 in ffn_amd/csrc/ffn_conv_split.h for activations,
-split_fp16x2 in ffn_hip.hip for weights):
+split_fp16x2 in ffn_hip.hip's set_weights for weights):
 
   hi  = fp16(v), round to nearest even, 11 significant bits (0 where |v| < 2^-14)
   res = fp16((v - hi) 2048)

@@ -74,7 +74,7 @@ class ShimHandle(EmulatedHandle):
   fail_step = None  # step number at which the device reports a voided step once
   fail_code = _lib.ERR_RANGE  # ... as FFN_ERR_RANGE, or FFN_ERR_FLOW
   total_native_calls = 0  # over all handles
-  # the speculative conv0_a launch of the HIP device (ffn_hip.hip SpecArgs),
+  # the speculative conv0_a launch of the HIP device (SpecArgs in ffn_conv0a.h),
   # emulated: [hints taken, steps made at a hinted position]; every such step
   # asserts that the device's choice (first hinted position that is valid on the
   # canvas as the previous step left it) is the position the loop then popped

@@ -663,7 +663,7 @@ def test_cells250_whole_volume_against_reference_minted_run(hip_exe, fib25_model
 
 # ---------------------------------------------------------------------------
 # round 3: the next step's conv0_a queued behind the paste (engine option
-# `speculate`, ffn_hip.hip SpecArgs)
+# `speculate`, SpecArgs in ffn_conv0a.h)
 # ---------------------------------------------------------------------------
 def test_speculative_conv0a_leaves_the_run_unchanged(hip_exe, fib25_model):
   """ffn_canvas_segment_at with and without the speculative conv0_a launch: the

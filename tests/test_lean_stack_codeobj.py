@@ -2,76 +2,19 @@
 them into libffn_hip.so: the point of the production form is what it does NOT carry --
 fewer scalar registers spilled to lanes between the tap loops, no more scratch, fewer
 kernel arguments.  Read from the AMDGPU metadata notes of the library's gfx950 code objects
-(llvm-readelf --notes), both kernels from the same build: relative checks, no numbers of a
+(tests/codeobj.py), both kernels from the same build: relative checks, no numbers of a
 particular compiler.  No GPU needed.
 """
 
-import os
+import collections
 import re
-import struct
-import subprocess
-
-import pytest
 
 from ffn_amd import _lib
-
-_MAGIC = b'__CLANG_OFFLOAD_BUNDLE__'
-
-
-def _readelf():
-  for root in (os.environ.get('ROCM_PATH', '/opt/rocm'), '/opt/rocm'):
-    path = os.path.join(root, 'llvm', 'bin', 'llvm-readelf')
-    if os.path.exists(path):
-      return path
-  pytest.fail('llvm-readelf of the ROCm tree not found')
-
-
-def _code_objects(lib_bytes):
-  """the gfx950 code objects of every offload bundle in the library"""
-  at = 0
-  while True:
-    at = lib_bytes.find(_MAGIC, at)
-    if at < 0:
-      return
-    (count,) = struct.unpack_from('<Q', lib_bytes, at + len(_MAGIC))
-    p = at + len(_MAGIC) + 8
-    for _ in range(count):
-      off, size, tlen = struct.unpack_from('<QQQ', lib_bytes, p)
-      triple = lib_bytes[p + 24:p + 24 + tlen].decode()
-      p += 24 + tlen
-      if 'gfx950' in triple and size:
-        yield lib_bytes[at + off:at + off + size]
-    at += len(_MAGIC)
-
-
-def _kernel_notes(tmp_path):
-  """{kernel symbol: {metadata field: int}} of every kernel in the library"""
-  assert os.path.exists(_lib.LIB_PATH), 'build the library first (__graft_entry__.build())'
-  with open(_lib.LIB_PATH, 'rb') as f:
-    data = f.read()
-  kernels = {}
-  for k, co in enumerate(_code_objects(data)):
-    path = tmp_path / ('co%d.elf' % k)
-    path.write_bytes(co)
-    text = subprocess.check_output([_readelf(), '--notes', str(path)], text=True)
-    # amdhsa.kernels: a list of maps, keys in alphabetical order; a kernel's '.args' list
-    # comes first, so the piece behind the last '- .' of a kernel holds its other fields
-    for block in re.split(r'\n\s*- \.', text):
-      names = re.findall(r'^\s*\.?name:\s+(\S+)', block, re.M)
-      if not names or 'kernarg_segment_size' not in block:
-        continue
-      fields = {}
-      for key in ('sgpr_spill_count', 'private_segment_fixed_size', 'kernarg_segment_size',
-                  'vgpr_spill_count'):
-        m = re.findall(r'\.%s:\s+(\d+)' % key, block)
-        if m:
-          fields[key] = int(m[-1])
-      kernels[names[-1].strip("'\"")] = fields
-  return kernels
+from tests import codeobj
 
 
 def test_production_stack_carries_less_than_the_lab_stack(tmp_path):
-  kernels = _kernel_notes(tmp_path)
+  kernels = codeobj.kernel_notes(_lib.LIB_PATH, tmp_path)
   forms = {}
   for name, fields in kernels.items():
     m = re.match(r'_ZN3ffn15conv32ps_kernelILb([01])E', name)
@@ -83,3 +26,20 @@ def test_production_stack_carries_less_than_the_lab_stack(tmp_path):
   assert prod['sgpr_spill_count'] < lab['sgpr_spill_count']
   assert prod['private_segment_fixed_size'] <= lab['private_segment_fixed_size']
   assert prod['kernarg_segment_size'] < lab['kernarg_segment_size']
+
+
+def test_every_kernel_is_in_one_code_object(tmp_path):
+  """Without relocatable device code a unit that names a kernel gets a device copy and a
+  registration of its own: an attribute set through one unit's copy would not reach a
+  launch made through another's.  So every kernel symbol of the library comes from ONE
+  unit.  Two kinds of names are a unit's own business and may recur: kernels in an
+  anonymous namespace, and the id-table templates of ffn_table.h, which every side unit
+  that keeps such a table instantiates for its own launches (no attribute is set on them)."""
+  where = collections.defaultdict(list)
+  for k, name, _ in codeobj.kernel_notes_by_object(_lib.LIB_PATH, tmp_path):
+    where[name].append(k)
+  assert len(where) > 100, 'the notes of the library were not read: %d kernels' % len(where)
+  assert any('conv32mt_kernel' in name for name in where)
+  twice = {name: ks for name, ks in where.items()
+           if len(ks) > 1 and not name.startswith(('_ZN12_GLOBAL__N_1', '_ZN9ffn_table'))}
+  assert not twice, twice
